@@ -27,9 +27,9 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-# Every frame slot / renderer instance launches on its own HIP stream, and the runtime deals streams to hardware queues (4 by
-# default): two streams on one queue serialise.  Ask for enough queues BEFORE the HIP runtime starts (it reads this once).
-# (main() chooses once it knows the configuration: 16 hardware queues, 24 where more than 16 streams are in use — N > 2, or C3's 20 frame slots)
+# Every frame slot / renderer instance launches on its own HIP stream, and the runtime deals streams to hardware queues: two streams
+# on one queue serialise.  The number of queues is left to whoever starts the job (a shared device has a fixed number of queue
+# slots for all its processes); a value the caller set is passed on to child runs as it is.
 QUEUES_SET_BY_CALLER = "GPU_MAX_HW_QUEUES" in os.environ
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.29 TB/s measured for a float4 copy)
@@ -100,7 +100,7 @@ def launch_ranks(n, argv):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    RFW_BENCH_LAUNCHED_BY=str(os.getpid()), HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
         if not QUEUES_SET_BY_CALLER:
-            env.pop("GPU_MAX_HW_QUEUES", None)  # (this process chose it for ONE rank: a child chooses for its own WORLD_SIZE)
+            env.pop("GPU_MAX_HW_QUEUES", None)  # (only a value the caller chose is passed on)
         # rank 0's stdout is the job's stdout (the ONE JSON line); what the other ranks print goes to stderr
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + argv, env=env,
                                       stdout=subprocess.PIPE if r == 0 else 2))  # (fd 2: this process's stderr, inherited as is)
@@ -180,7 +180,12 @@ def main():
                     help="the headline run (atrium1m, max path length 1, one GPU) also runs BASELINE.json's other single-GPU configurations — C2, C3 and the "
                          "path-traced C4 — as short child runs of this script, each with its own oracle check, and reports them in config.modes; this skips them")
     ap.add_argument("--baseline-steps", type=int, default=200, help="timed frames of each of those child runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: the frame's accumulator "
+                         "and a fixed, seeded sample of its finished framebuffer (float32; the sample's pixel indices float64; at most 64 MB in all); the inputs are the same from run to run")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
 
     # ---- who runs the ranks.  `--gpus N` is the number of ranks, whoever starts them:
     #   * under a launcher (python -m torch.distributed.run: WORLD_SIZE = N in the environment) this process IS one of the N ranks;
@@ -194,8 +199,6 @@ def main():
     if args.gpus > 1 and env_world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={env_world} ranks: refusing to report a number for a job of another size")
     world = args.gpus
-    if not QUEUES_SET_BY_CALLER:  # (before anything starts the HIP runtime)
-        os.environ["GPU_MAX_HW_QUEUES"] = "24" if (world > 2 or args.workload == "spheres10k") else "16"
     rank = int(os.environ.get("RANK", "0")) if world > 1 else 0
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
     # RFW_BENCH_DIST_BACKEND=gloo is a TEST HOOK: it lets two ranks share one GPU (RCCL refuses duplicate devices) so the
@@ -517,6 +520,7 @@ def main():
         bes[0].wait_downloads()
         lb, lframes = state["last"]
         timed_frames_gpu = [(0, np.array(check0, copy=True)), (lframes[-1], lb.accumulator())]
+    dumped = dump_outputs(args.dump_outputs, state["last"]) if (args.dump_outputs and rank == 0) else None
     # Sharded frame: is what the all-gather + assemble left on this rank the frame one GPU renders alone?  (static scenes only)
     shard_check = None
     if world > 1 and rank == 0 and not animated and state["last"] is not None:
@@ -786,12 +790,44 @@ def main():
                 res["all"] = all(v["bit_identical"] for v in res.values())
                 out["config"]["timed_frame_equals_oracle"] = res
         out["config"]["modes"].update(baseline_rows)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     for b in bes:
         b.close()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what the last timed step handed its caller, for comparing two builds output for output.  `last` = (instance, view
+    indices of the frames its last call traced); the last of those frames is written: its accumulator in full (float32 h x w x 4) where it
+    fits the 64 MB budget, else a seeded sample of its pixels like the framebuffer's (float32 n x 4, the finished frame, with the flat
+    pixel indices beside it).  Returns {name: [shape, dtype]} for the result line."""
+    import numpy as np
+    b, frames = last
+    f = len(frames) - 1
+    acc = b.accumulator_at(f) if len(frames) > 1 else b.accumulator()
+    fb = b.framebuffer_at(f) if len(frames) > 1 else b.framebuffer()
+    n_pix = acc.shape[0] * acc.shape[1]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pix, size=min(DUMP_SAMPLE_PIXELS, n_pix), replace=False)).astype(np.int64)
+    arrays = {"framebuffer_sample": fb.reshape(n_pix, 4)[idx], "framebuffer_sample_pixels": idx.astype(np.float64)}
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())
+    if acc.nbytes <= room:
+        arrays["accumulator"] = acc
+    else:
+        arrays["accumulator_sample"] = acc.reshape(n_pix, 4)[idx]
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: [list(a.shape), str(a.dtype)] for name, a in arrays.items()}
 
 
 def baseline_configs(args):
@@ -806,7 +842,7 @@ def baseline_configs(args):
             ("BASELINE config 4 (~1 M triangles path traced with NEE, max path length 3)", ["--workload", "atrium1m", "--max-path-length", "3"], True))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     if not QUEUES_SET_BY_CALLER:
-        env.pop("GPU_MAX_HW_QUEUES", None)  # (this process chose it for ITS configuration: a child chooses for its own — C3 runs 20 slots over 24 queues)
+        env.pop("GPU_MAX_HW_QUEUES", None)  # (only a value the caller chose is passed on)
     for name, extra, with_modes in todo:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.baseline_steps), "--warmup", "20", "--no-baseline-configs",
                "--cpu-seconds", "3", "--mode-frames", "32"] + extra + ([] if with_modes else ["--no-modes"]) + (["--procedural"] if args.procedural else [])

@@ -266,9 +266,10 @@ RFW_HIP_API int rfw_hip_comm_init(void* instance, const void* id128, uint32_t ra
 RFW_HIP_API int rfw_hip_comm_destroy(void* instance);
 /* TEST TRANSPORT.  `world` instances of ONE process on ONE device, created with options.rank = 0 .. world - 1, join the hub `hub_key` instead of
  * a communicator: their render() calls then exchange tiles as with rfw_hip_comm_init — same packing, same per-slot gather buffers, same
- * ordering of the frame slots' collectives, same de-tiling — but the bytes are moved by device copies the LAST rank to call enqueues.  Every
- * rank must call render() for a frame before anyone waits for that frame; a rank that never does shows up as RFW_HIP_E_DEVICE ("a peer's
- * flag did not arrive", option p2p_timeout_ms) from the others' reads.  rfw_hip_comm_destroy leaves the hub.  No RCCL is involved. */
+ * ordering of the frame slots' collectives, same de-tiling — but the bytes are moved by device copies the LAST rank to call enqueues.  A
+ * rank's render() returns once every rank has called render() for that frame, so the ranks call it from threads of their own; a rank that
+ * never does shows up as RFW_HIP_E_DEVICE ("a peer did not arrive", option p2p_timeout_ms) from the others' render() calls.
+ * rfw_hip_comm_destroy leaves the hub.  No RCCL is involved. */
 RFW_HIP_API int rfw_hip_comm_init_loopback(void* instance, uint64_t hub_key, uint32_t rank, uint32_t world);
 
 /* The same exchange WITHOUT a collective library (SURVEY.md §8e's alternative): every rank stores its tiles straight into its peers'

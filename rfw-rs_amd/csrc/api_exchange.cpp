@@ -1,6 +1,9 @@
 // api_exchange.cpp — the sharded frame: what a rank sends and what it does with what it receives — packing, the RCCL all-gather
 // inside the library (rfw_hip_comm_*), the exchange by peer stores (rfw_hip_p2p_*), de-tiling.
 #include "api_internal.h"
+#include <algorithm>
+#include <chrono>
+#include <condition_variable>
 
 using namespace rfwapi;
 
@@ -195,24 +198,38 @@ int rfw_hip_comm_destroy(void* inst)
 // ---- the loop-back transport (rfw_hip_comm_init_loopback): W instances of ONE process, one per rank, exchange their tiles through a hub
 // instead of a communicator.  It exists so that everything around the collective — the packing, the per-slot gather buffers, the event chain
 // that orders the slots' collectives (comm_chain), de-tiling on the presenting rank, a rank that never arrives — runs where there is one
-// GPU and no second process.  Semantics of ncclAllGather on a stream: the call returns at once; what follows it on the
-// caller's stream runs when every rank's contribution is in every rank's receive buffer.  Here: the caller records "my tiles are packed",
-// enqueues a wait for its own flag word, and the LAST rank to arrive (host side) enqueues the W x W copies on the hub's stream behind
-// every rank's event, then sets every rank's flag.
+// GPU and no second process.  What follows the gather on the caller's stream runs when every rank's contribution is in
+// every rank's receive buffer, as after ncclAllGather.  Here: the caller records "my tiles are packed" and joins the slot's gather on the
+// host; the LAST rank to arrive enqueues the W x W copies on the hub's stream behind every rank's event and records the slot's `gathered`
+// event; every rank's stream waits for that event.  A rank returns only once the copies are enqueued (the ranks run on threads of their
+// own), so no stream ever waits for work enqueued after the wait: the exchange needs no hardware queue per stream.
 namespace rfwapi {
 struct LoopHub {
     std::mutex mu;
+    std::condition_variable cv;
     uint32_t world = 0, n_slots = 0;
     int device = 0;
     hipStream_t stream = nullptr;
-    uint32_t* flags = nullptr; // [slot][rank]: gathers completed
+    std::vector<hipEvent_t> gathered; // [slot]: the slot's last gather is in every receive buffer
     std::vector<Instance*> owner; // per rank (nullptr: not joined / left)
     struct Call { Instance* inst; uint64_t words; };
     std::vector<std::vector<Call>> pending; // [slot]
-    std::vector<uint32_t> done;             // [slot]
+    std::vector<uint32_t> done;             // [slot]: gathers enqueued
 };
 static std::mutex g_hubs_mu;
 static std::map<uint64_t, LoopHub*> g_hubs;
+
+static hipError_t loop_enqueue_gather(LoopHub* H, uint32_t slot, uint64_t n_words)
+{
+    const auto& calls = H->pending[slot];
+    for (const auto& c : calls)
+        if (hipError_t e = hipStreamWaitEvent(H->stream, c.inst->loop_sent, 0); e != hipSuccess) return e;
+    for (const auto& dst : calls)
+        for (const auto& src : calls)
+            if (hipError_t e = hipMemcpyAsync(dst.inst->d_recv.ptr + (size_t)src.inst->rank * n_words, src.inst->d_send.ptr, n_words * sizeof(float),
+                                              hipMemcpyDeviceToDevice, H->stream); e != hipSuccess) return e;
+    return hipEventRecord(H->gathered[slot], H->stream);
+}
 
 int loop_all_gather(Instance* I, hipStream_t s, uint64_t n_words)
 {
@@ -222,27 +239,29 @@ int loop_all_gather(Instance* I, hipStream_t s, uint64_t n_words)
     if (slot >= H->n_slots) return fail(I, RFW_HIP_E_STATE, "loop-back exchange: this instance has more frame slots than the hub was made for");
     if (!I->loop_sent) HIP_TRY(I, hipEventCreateWithFlags(&I->loop_sent, hipEventDisableTiming));
     HIP_TRY(I, hipEventRecord(I->loop_sent, s)); // (behind pack_slabs)
-    const uint32_t want = ++I->loop_seq;
-    launch_p2p_wait(s, H->flags + (size_t)slot * H->world, I->rank, 1u, want, C->p2p.timeout_ticks, I->overflow_dev + 1);
-    std::lock_guard<std::mutex> g(H->mu);
+    ++I->loop_seq;
+    std::unique_lock<std::mutex> g(H->mu);
     auto& calls = H->pending[slot];
     for (const auto& c : calls)
         if (c.inst->rank == I->rank) return fail(I, RFW_HIP_E_STATE, "loop-back exchange: this rank joined the slot's gather twice before the others arrived");
+    for (const auto& c : calls)
+        if (c.words != n_words) return fail(I, RFW_HIP_E_STATE, "loop-back exchange: the ranks contribute slabs of different sizes");
     calls.push_back({I, n_words});
-    if (calls.size() < H->world) return RFW_HIP_OK;
-    // the last rank of this gather: move everything, on the hub's stream, behind every rank's packing
-    for (const auto& c : calls) {
-        if (c.words != n_words) { calls.clear(); return fail(I, RFW_HIP_E_STATE, "loop-back exchange: the ranks contribute slabs of different sizes"); }
-        HIP_TRY(I, hipStreamWaitEvent(H->stream, c.inst->loop_sent, 0));
+    if (calls.size() < H->world) { // wait on the host for the last rank (p2p_timeout_ms; the option counts 100 MHz ticks)
+        const uint32_t round = H->done[slot];
+        if (!H->cv.wait_for(g, std::chrono::microseconds(C->p2p.timeout_ticks / 100u), [&] { return H->done[slot] != round; })) {
+            calls.erase(std::remove_if(calls.begin(), calls.end(), [&](const LoopHub::Call& c) { return c.inst == I; }), calls.end());
+            return fail(I, RFW_HIP_E_DEVICE, "loop-back exchange: a peer did not arrive within p2p_timeout_ms (a rank did not take part: the frame is incomplete)");
+        }
+    } else { // the last rank of this gather: move everything, on the hub's stream, behind every rank's packing
+        const hipError_t e = loop_enqueue_gather(H, slot, n_words);
+        calls.clear();
+        if (e != hipSuccess) return fail(I, RFW_HIP_E_DEVICE, std::string("loop-back exchange: ") + hipGetErrorString(e));
+        H->done[slot]++;
+        H->cv.notify_all();
     }
-    for (const auto& dst : calls)
-        for (const auto& src : calls)
-            HIP_TRY(I, hipMemcpyAsync(dst.inst->d_recv.ptr + (size_t)src.inst->rank * n_words, src.inst->d_send.ptr, n_words * sizeof(float), hipMemcpyDeviceToDevice, H->stream));
-    P2PTargets t;
-    for (uint32_t r = 0; r < H->world; r++) t.p[r] = H->flags + (size_t)slot * H->world + r;
-    launch_p2p_signal(H->stream, t, H->world, ++H->done[slot]);
-    HIP_TRY(I, hipGetLastError());
-    calls.clear();
+    // (a later gather of this slot needs this rank again, so the event still holds THIS gather)
+    HIP_TRY(I, hipStreamWaitEvent(s, H->gathered[slot], 0));
     return RFW_HIP_OK;
 }
 void loop_leave(Instance* owner)
@@ -264,7 +283,8 @@ void loop_leave(Instance* owner)
         if (it->second == H) { g_hubs.erase(it); break; }
     (void)hipSetDevice(H->device);
     if (H->stream) { (void)hipStreamSynchronize(H->stream); (void)hipStreamDestroy(H->stream); }
-    if (H->flags) (void)hipFree(H->flags);
+    for (hipEvent_t e : H->gathered)
+        if (e) (void)hipEventDestroy(e);
     delete H;
 }
 } // namespace rfwapi
@@ -285,17 +305,13 @@ int rfw_hip_comm_init_loopback(void* inst, uint64_t hub_key, uint32_t rank, uint
         if (it == g_hubs.end()) {
             H = new LoopHub();
             H->world = world; H->n_slots = (uint32_t)I->slots.size() + 1u; H->device = I->device;
-            H->owner.assign(world, nullptr); H->pending.resize(H->n_slots); H->done.assign(H->n_slots, 0u);
-            const size_t fb = (size_t)H->n_slots * world * sizeof(uint32_t);
+            H->owner.assign(world, nullptr); H->pending.resize(H->n_slots); H->done.assign(H->n_slots, 0u); H->gathered.assign(H->n_slots, nullptr);
             hipError_t e = hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking);
-            if (e == hipSuccess && hipExtMallocWithFlags((void**)&H->flags, fb, hipDeviceMallocUncached) != hipSuccess) {
-                (void)hipGetLastError();
-                e = hipMalloc((void**)&H->flags, fb);
-            }
-            if (e == hipSuccess) e = hipMemset(H->flags, 0, fb);
+            for (uint32_t k = 0; k < H->n_slots && e == hipSuccess; k++) e = hipEventCreateWithFlags(&H->gathered[k], hipEventDisableTiming);
             if (e != hipSuccess) {
                 if (H->stream) (void)hipStreamDestroy(H->stream);
-                if (H->flags) (void)hipFree(H->flags);
+                for (hipEvent_t ev : H->gathered)
+                    if (ev) (void)hipEventDestroy(ev);
                 delete H;
                 return fail(I, RFW_HIP_E_DEVICE, std::string("comm_init_loopback: ") + hipGetErrorString(e));
             }

@@ -67,7 +67,7 @@ int main(int argc, char** argv)
         opt.device = -1;
         opt.max_path_length = path_length;
         opt.world = 1;
-        opt.frames_in_flight = 4; // GPU_MAX_HW_QUEUES >= 4 is the runtime's default
+        opt.frames_in_flight = 4; // one HIP stream per frame slot
         std::unique_ptr<rfw::HipBackend> renderer(rfw::HipBackend::init(width, height, 1.0, &opt));
 
         const uint64_t px = (uint64_t)width * height;

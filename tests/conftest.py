@@ -1,3 +1,4 @@
+import functools
 import os
 import sys
 
@@ -10,6 +11,11 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
+    if has_gpu():
+        # torch's HIP runtime and the product's share the process: start torch's before anything loads the product's library, the order
+        # bench.py has.  Loaded the other way round with the CPU tests in between, one of the two runtimes is left without a device.
+        import torch
+        torch.cuda.init()
 
 
 @pytest.fixture(scope="session", autouse=True)
@@ -22,12 +28,13 @@ def _built():
         __graft_entry__.build()
 
 
+@functools.lru_cache(maxsize=None)
 def has_gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
+    """Asked in a child process, so that the test process starts torch's HIP runtime only where pytest_configure does."""
+    import subprocess
+    r = subprocess.run([sys.executable, "-c", "import torch, sys; sys.exit(0 if torch.cuda.is_available() else 1)"],
+                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return r.returncode == 0
 
 
 def rel_l2(a, b):

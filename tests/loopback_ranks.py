@@ -1,11 +1,14 @@
 """Three ranks of ONE process exchanging tiles through the library's loop-back hub (rfw_hip_comm_init_loopback): run by
-tests/test_gpu_parity.py::test_library_exchange_through_the_loopback_hub in a process of its own (GPU_MAX_HW_QUEUES is read once).
+tests/test_gpu_parity.py::test_library_exchange_through_the_loopback_hub in a process of its own.
     python3 tests/loopback_ranks.py <gather format 0|1|2> <present rank, -1 = every rank de-tiles>
 What the ranks end up with is the single-GPU frame, bit for bit — after every frame, and again after six frames in flight over three frame
-slots per rank (the slots' gathers chained by the same events as with ncclAllGather).  Then the failure only N > 1 has: a rank that never
-renders its frame is reported by the others' reads."""
+slots per rank (the slots' gathers chained by the same events as with ncclAllGather).  Every rank runs its render() calls on a thread of
+its own, as ranks of one process do: a rank's call returns once every rank has joined the gather.  Then the failure only N > 1 has: a rank
+that never renders its frame is reported by the others' render() calls."""
 import os
 import sys
+import threading
+import time
 
 import numpy as np
 
@@ -72,25 +75,40 @@ def check(i, what):
             be.download_frame(dst); be.wait_downloads()
             assert np.array_equal(dst, pres), (what, i, r)
 
+def render_all(order, v):
+    """every rank of `order` calls render(v) on a thread of its own, started in that order (a rank returns once all have joined the
+    gather); returns what each call raised, None where it returned"""
+    errors = [None] * len(order)
+
+    def run(k, be):
+        try:
+            be.render(v)
+        except BackendError as e:
+            errors[k] = e
+    threads = [threading.Thread(target=run, args=(k, be)) for k, be in enumerate(order)]
+    for t in threads:
+        t.start()
+        time.sleep(0.002)
+    for t in threads:
+        t.join()
+    return errors
+
+
 for i, v in enumerate(views):                          # one frame at a time
-    for be in ranks:
-        be.render(v)
+    assert render_all(ranks, v) == [None] * world
     check(i, "frame by frame")
 for rep in range(3):                                   # six frames in flight over three slots per rank, ranks issued in changing order
     for i, v in enumerate(views):
-        for be in (ranks if (i + rep) % 2 == 0 else ranks[::-1]):
-            be.render(v)
+        errs = render_all(ranks if (i + rep) % 2 == 0 else ranks[::-1], v); assert errs == [None] * world, (rep, i, errs)
     check(len(views) - 1, "six frames in flight")
-# a rank that never arrives
+# a rank that never arrives: the others' render() calls fail once p2p_timeout_ms has passed
 for be in ranks:
     be.set_option("p2p_timeout_ms", 300)
-ranks[0].render(views[0])
-ranks[1].render(views[0])
-reader = ranks[present_rank if present_rank >= 0 else 0]
-with raises(BackendError, match="did not arrive"):
-    reader.device_synchronize()
-    reader.framebuffer() if fmt != 2 else reader.download_frame(reader.host_frame(presented=True))
-    reader.wait_downloads()
+errors = render_all(ranks[:2], views[0])
+for e in errors:
+    with raises(BackendError, match="did not arrive"):
+        if e is not None:
+            raise e
 for be in ranks + [full]:
     be.close()
 

@@ -1032,10 +1032,8 @@ def test_library_exchange_through_the_loopback_hub(fmt, present_rank):
     """the exchange INSIDE the library (render() packs, gathers, de-tiles: what `bench.py --collective native` runs over RCCL
     on a multi-GPU node) cannot be rehearsed with world > 1 on one device through RCCL itself.  rfw_hip_comm_init_loopback stands in for the
     communicator only (tests/loopback_ranks.py: three ranks in one process, three frame slots each, six frames in flight, every gather format,
-    a rank that never arrives).  In a process of its own: like several NCCL ranks driven by one process, every stream involved needs a
-    hardware queue of its own (a rank's wait must not sit in front of the copies it waits for), and the runtime reads GPU_MAX_HW_QUEUES once."""
+    a rank that never arrives; every rank on a thread of its own).  In a process of its own."""
     import subprocess, sys
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="24")
     out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "loopback_ranks.py"), str(fmt), str(present_rank)],
-                         env=env, capture_output=True, text=True, timeout=600)
+                         capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "LOOPBACK OK" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])

@@ -21,8 +21,8 @@ import isa_stats  # noqa: E402
 
 
 @pytest.fixture(scope="module")
-def listing():
-    path, stderr = isa_stats.build()
+def listing(tmp_path_factory):
+    path, stderr = isa_stats.build(out_dir=str(tmp_path_factory.mktemp("rfw_isa")))
     return path, stderr, isa_stats.parse(path)
 
 

@@ -24,8 +24,8 @@ def makefile_flags():
     return m.group(1).replace("$(ARCH)", "gfx950").split()
 
 
-def build(source="kernels.hip", extra=()):
-    out_dir = os.path.join(tempfile.gettempdir(), "rfw_isa")
+def build(source="kernels.hip", extra=(), out_dir=None):
+    out_dir = out_dir or os.path.join(tempfile.gettempdir(), "rfw_isa")
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, os.path.splitext(source)[0] + ".s")
     cmd = ["/opt/rocm/bin/hipcc"] + makefile_flags() + list(extra) + ["--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, source)]
