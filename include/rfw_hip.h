@@ -184,7 +184,30 @@ RFW_HIP_API int rfw_hip_set_materials(void* instance, const rfw_device_material*
 RFW_HIP_API int rfw_hip_set_textures(void* instance, const rfw_texture_data* textures, uint32_t num, const uint32_t* changed);
 /* :57 synchronize — builds/refits acceleration structures for what changed. */
 RFW_HIP_API int rfw_hip_synchronize(void* instance);
-/* :60 render — one sample per pixel per call, accumulating (gpu-rt/src/lib.rs:1685-1731). */
+/* :60 render — one sample per pixel per call, accumulating (gpu-rt/src/lib.rs:1685-1731).
+ * `mode` is rfw_backend::RenderMode (crates/rfw-backend/src/lib.rs:10-18), values below.  DEFAULT and every unknown value (>= 7) path
+ * trace: the frame is sqrt(acc / n).  Modes 1-6 take one sample per call of the same jittered camera ray DEFAULT would trace, ADD the
+ * per-sample value of the primary hit (as k_shade sees it at bounce 0) to the accumulator, and finalise the LINEAR mean acc / n (the
+ * presented BGRA8 image is the sRGB encoding of that mean).  A camera ray that misses gives (0, 0, 0, 0).
+ *   NORMAL         world-space shading normal after the normal map and the back-facing flip, w = 0 (emissive triangles: no normal map)
+ *   ALBEDO         the material colour after the diffuse map, before tinting (emissive triangles: the stored colour), w = 0
+ *   GBUFFER        hit point P = O + t D in xyz, w = t
+ *   SCREEN_SPACE   view-space position (dot(P - pos, r), dot(P - pos, u), dot(P - pos, d), 1), r, u, d the normalised right, up, direction
+ *   SSAO           ray-traced ambient occlusion: the fraction of "ao_samples" cosine-weighted rays about the faced geometric normal that
+ *                  meet nothing within "ao_radius", in rgb, w = 0
+ *   FILTERED_SSAO  the accumulator of SSAO; the frame is an edge-aware filter of acc.x / n guided by the primary hit's normal and
+ *                  distance (DESIGN.md "Render modes").  With world > 1 the guides stay on their ranks: the frame finalises as SSAO.
+ * A change of mode starts a new image (as a change of view); render_batch / render_samples always render DEFAULT.  Options "ao_samples"
+ * (1-8, default 4) and "ao_radius" (world units; 0 = 5 % of the diagonal of the scene's bounds, the default) restart accumulation. */
+enum {
+    RFW_HIP_RENDER_DEFAULT = 0,
+    RFW_HIP_RENDER_NORMAL = 1,
+    RFW_HIP_RENDER_ALBEDO = 2,
+    RFW_HIP_RENDER_GBUFFER = 3,
+    RFW_HIP_RENDER_SCREEN_SPACE = 4,
+    RFW_HIP_RENDER_SSAO = 5,
+    RFW_HIP_RENDER_FILTERED_SSAO = 6
+};
 RFW_HIP_API int rfw_hip_render(void* instance, const rfw_mat4* view_2d, const rfw_camera_view_3d* view_3d, uint32_t mode);
 /* :63 resize */
 RFW_HIP_API int rfw_hip_resize(void* instance, uint32_t width, uint32_t height, double scale);
@@ -203,7 +226,7 @@ RFW_HIP_API int rfw_hip_set_skins(void* instance, const rfw_skin_data* skins, ui
 RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
 /* Options (unknown keys are an error).  The trait has none: these are the knobs a host outside the trait may turn.
  *   rendering      "max_path_length" (1 = primary + shadow), "clamp_value", "nee" (0 / 1), "sample_count", "sky_r" / "sky_g" / "sky_b",
- *                  "texture_array" (gpu-rt's 1024^2 x 5 texture array, default 1)
+ *                  "texture_array" (gpu-rt's 1024^2 x 5 texture array, default 1), "ao_samples" / "ao_radius" (render modes 5, 6)
  *   measurement    "count_traversal" (node / triangle / instance counters of the next frames), "timing" (HIP events per kernel)
  *   ray order      "shadow_order" 0 | 1 | 2 (which end any-hit traversals start from; the image is the same under every order),
  *                  "sort_extension_rays" 0 never | 1 always | 2 batches whose bounces do not stream (default),

@@ -4,6 +4,7 @@ argument meaning and order follow the trait; every method is one call into librf
 (hand-written HIP for gfx950).  There is no Python or CPU fallback: if the library is missing
 or no HIP device is present, construction raises."""
 import ctypes as C
+import enum
 import os
 
 import numpy as np
@@ -136,6 +137,17 @@ class BackendError(RuntimeError):
     pass
 
 
+class RenderMode(enum.IntEnum):
+    """rfw_backend::RenderMode (crates/rfw-backend/src/lib.rs:10-18), the `mode` of render(); include/rfw_hip.h RFW_HIP_RENDER_*."""
+    DEFAULT = 0
+    NORMAL = 1
+    ALBEDO = 2
+    GBUFFER = 3
+    SCREEN_SPACE = 4
+    SSAO = 5
+    FILTERED_SSAO = 6
+
+
 class HipBackend:
     """`impl Backend for HipBackend` — see crates/rfw-backend/src/lib.rs:35-82 for each method."""
 
@@ -220,7 +232,7 @@ class HipBackend:
         self._check(self._l.rfw_hip_synchronize(self._h))
 
     def render(self, view_3d, view_2d=None, mode=0):
-        self._check(self._l.rfw_hip_render(self._h, None, C.byref(view_3d), mode))
+        self._check(self._l.rfw_hip_render(self._h, None, C.byref(view_3d), int(mode)))  # RenderMode, or any int (unknown values render DEFAULT)
 
     def resize(self, window_size, scale_factor=1.0):
         self._check(self._l.rfw_hip_resize(self._h, window_size[0], window_size[1], scale_factor))

@@ -41,7 +41,7 @@ void pack_slabs(Instance* I, hipStream_t s, void* dst, uint32_t frames)
     const uint64_t n = (uint64_t)I->capacity * frames;
     const uint32_t f = scene_of(I)->gather_format;
     if (f == 0) launch_pack_rgb(s, I->d_acc_slab.ptr, (float*)dst, n);
-    else launch_pack_finished(s, I->d_acc_slab.ptr, dst, n, std::max(1u, I->sample_count), f, srgb_steps());
+    else launch_pack_finished(s, I->d_acc_slab.ptr, dst, n, std::max(1u, I->sample_count), f, srgb_steps(), I->render_mode != RFW_HIP_RENDER_DEFAULT);
 }
 // gathered = [rank][frame][slab] in the instance's gather format -> the row-major frame(s)
 int assemble_gathered(Instance* I, hipStream_t s, const void* gathered, uint32_t k, uint32_t samples)
@@ -50,7 +50,7 @@ int assemble_gathered(Instance* I, hipStream_t s, const void* gathered, uint32_t
     cam.batch = k;
     const uint32_t fmt = scene_of(I)->gather_format;
     if (fmt == 0) {
-        launch_assemble(s, cam, gathered, true, false, I->cap_v, I->d_frame_out.ptr, samples);
+        launch_assemble(s, cam, gathered, true, false, I->cap_v, I->d_frame_out.ptr, samples, I->render_mode != RFW_HIP_RENDER_DEFAULT); // (mode 6 finalises as 5 here)
         I->acc_source = gathered; I->acc_source_rgb = true; I->acc_source_batch = k;
     } else if (fmt == 1) {
         launch_assemble_finished(s, cam, gathered, I->cap_v, 1u, I->d_frame_out.ptr, nullptr);

@@ -84,6 +84,7 @@ int alloc_paths(Instance* I)
     HIP_TRY(I, I->d_counters.ensure(2 * kMaxSub));
     HIP_TRY(I, hipMemsetAsync(I->d_counters.ptr, 0, 2 * kMaxSub * sizeof(QueueCounters), I->stream));
     I->sample_count = 0;
+    I->ao_rounds = 0; // (the shadow queue was reallocated: no AO rays to report)
     return RFW_HIP_OK;
 }
 
@@ -192,7 +193,37 @@ constexpr int kEvBlit = EV_KERNEL_BASE + 2 * (kMaxBounces * kKernelsPerBounce);
 
 hipEvent_t* ring_events(Instance* I, int slot, uint32_t sub) { return I->ring.data() + ((size_t)slot * I->substreams + sub) * kNumEvents; }
 
-int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool samples)
+// option "ao_radius" = 0: 5 % of the diagonal of the world bounds of the scene's instances (mesh boxes as handed over, through the instance
+// matrices), on the host, once per scene version — at the first ambient occlusion frame after a synchronize() that changed the scene
+static float ao_radius_of(Instance* I)
+{
+    if (I->ao_radius > 0.0f) return I->ao_radius;
+    Instance* O = scene_of(I);
+    if (O->ao_auto_version != O->scene_version) {
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const auto& kv : O->inst_lists) {
+            const rfw_aabb& b = kv.second.local_aabb;
+            for (const rfw_mat4& m : kv.second.matrices) {
+                bool zero = true;
+                for (int c = 0; c < 16; c++) zero = zero && m.m[c] == 0.0f;
+                if (zero) continue; // a removed slot
+                for (int c = 0; c < 8; c++) {
+                    const float x = (c & 1) ? b.max[0] : b.min[0], y = (c & 2) ? b.max[1] : b.min[1], z = (c & 4) ? b.max[2] : b.min[2];
+                    const float w[3] = {m.m[0] * x + m.m[4] * y + m.m[8] * z + m.m[12], m.m[1] * x + m.m[5] * y + m.m[9] * z + m.m[13],
+                                        m.m[2] * x + m.m[6] * y + m.m[10] * z + m.m[14]};
+                    for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], w[a]); hi[a] = std::max(hi[a], w[a]); }
+                }
+            }
+        }
+        double d2 = 0.0;
+        for (int a = 0; a < 3; a++) d2 += hi[a] >= lo[a] ? ((double)hi[a] - lo[a]) * ((double)hi[a] - lo[a]) : 0.0;
+        O->ao_auto_radius = d2 > 0.0 ? (float)(0.05 * std::sqrt(d2)) : 1.0f;
+        O->ao_auto_version = O->scene_version;
+    }
+    return O->ao_auto_radius;
+}
+
+int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool samples, uint32_t mode)
 {
     const rfw_camera_view_3d& view = views[0];
     HIP_TRY(I, hipSetDevice(I->device));
@@ -210,7 +241,8 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         I->tables_used = S->tables_version;
         if (I->tables_oldest_pending == ~0ull) I->tables_oldest_pending = S->tables_version;
     }
-    if ((I->have_last_view && std::memcmp(&I->last_view, &view, sizeof(view)) != 0) || I->after_batch) I->sample_count = 0;
+    if ((I->have_last_view && (std::memcmp(&I->last_view, &view, sizeof(view)) != 0 || mode != I->render_mode)) || I->after_batch) I->sample_count = 0;
+    I->render_mode = mode; // (a change of mode starts a new image, as a change of view does)
     I->after_batch = k > 1 && !samples; // the frames of a batch are complete images: whatever follows starts a new one
     I->last_view = view;
     I->have_last_view = true;
@@ -232,6 +264,9 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
     const int slot = (int)(I->frame_index % kTimingRing);
     I->events = ring_events(I, slot, 0);
     const uint32_t bounces = std::min<uint32_t>(I->max_path_length, kMaxBounces);
+    const bool ao = mode >= RFW_HIP_RENDER_SSAO;
+    const uint32_t ao_rounds = ao ? I->ao_samples : 0u;
+    if (ao) HIP_TRY(I, I->d_ao_guide.ensure((size_t)I->width * I->height));
 
     if (tm) (void)hipEventRecord(I->events[EV_FRAME0], main);
     // queue counters: this frame takes the block the previous frame's k_primary cleared (alloc_paths cleared both), and clears the other
@@ -274,7 +309,27 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
             v.p1[0] = views[f].p1.x; v.p1[1] = views[f].p1.y; v.p1[2] = views[f].p1.z; v.pad2 = 0.0f;
         }
     }
-    for (uint32_t b = 0; b < bounces; b++) { // gpu-rt/src/lib.rs:1708-1728 without the read-back; stage by stage across the sub-shards
+    if (mode != RFW_HIP_RENDER_DEFAULT) {
+        // render modes 1-6 (aov.inc): the camera rays of mode 0, then the mode's value at their hits — or the ambient occlusion rays, traced
+        // through the shadow queue one round per launch (k_shadow adds to the accumulator with one writer per slot and launch)
+        const float radius = ao ? ao_radius_of(I) : 0.0f;
+        const float dir[3] = {view.direction.x, view.direction.y, view.direction.z};
+        for (uint32_t s = 0; s < S; s++) {
+            hipEvent_t* ev = ring_events(I, slot, s);
+            if (tm) (void)hipEventRecord(ev[ev_index(0, 0, 0)], st[s]);
+            launch_primary(st[s], cam[s], sc[s], p[s], count);
+            if (tm) (void)hipEventRecord(ev[ev_index(0, 0, 1)], st[s]);
+            if (tm) (void)hipEventRecord(ev[ev_index(0, 1, 0)], st[s]);
+            launch_aov(st[s], cam[s], sc[s], p[s], mode, ao_rounds, radius, I->d_ao_guide.ptr, dir);
+            if (tm) (void)hipEventRecord(ev[ev_index(0, 1, 1)], st[s]);
+            if (tm) (void)hipEventRecord(ev[ev_index(0, 2, 0)], st[s]);
+        }
+        for (uint32_t r = 0; r < ao_rounds; r++)
+            for (uint32_t s = 0; s < S; s++) launch_shadow(st[s], cam[s], sc[s], p[s], r, count);
+        for (uint32_t s = 0; s < S; s++)
+            if (tm) (void)hipEventRecord(ring_events(I, slot, s)[ev_index(0, 2, 1)], st[s]);
+    }
+    for (uint32_t b = 0; b < bounces && mode == RFW_HIP_RENDER_DEFAULT; b++) { // gpu-rt/src/lib.rs:1708-1728 without the read-back; stage by stage across the sub-shards
         for (uint32_t s = 0; s < S; s++) {
             hipEvent_t* ev = ring_events(I, slot, s);
             if (tm) (void)hipEventRecord(ev[ev_index(b, 0, 0)], st[s]);
@@ -348,7 +403,8 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         if (prc != RFW_HIP_OK) return prc;
     } else if (I->world <= 1) // de-tile the sub-slabs into the linear accumulator / tonemapped frame (blit.comp:15-23)
     {
-        launch_assemble(main, cam[0], I->d_acc_slab.ptr, false, false, I->cap_v, I->d_frame_out.ptr, I->sample_count);
+        if (mode == RFW_HIP_RENDER_FILTERED_SSAO) launch_ao_filter(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_ao_guide.ptr, I->d_frame_out.ptr, I->sample_count);
+        else launch_assemble(main, cam[0], I->d_acc_slab.ptr, false, false, I->cap_v, I->d_frame_out.ptr, I->sample_count, mode != RFW_HIP_RENDER_DEFAULT);
         I->acc_source = I->d_acc_slab.ptr; I->acc_source_rgb = false; I->acc_source_batch = frames_out;
     }
     if (I->external_slab) // this rank's contribution to the all-gather, [frame][sub-shard][slot] in the instance's gather format
@@ -356,9 +412,11 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
     if (tm) (void)hipEventRecord(I->events[kEvBlit + 1], main);
     if (tm) (void)hipEventRecord(I->events[EV_FRAME1], main);
     HIP_TRY(I, hipGetLastError());
-    I->last_bounces = bounces;
-    I->ring_bounces[slot] = tm ? bounces : 0;
-    I->ring_nee[slot] = nee;
+    const uint32_t passes = mode == RFW_HIP_RENDER_DEFAULT ? bounces : 1u; // (modes 1-6: one "bounce", its shadow stage = the AO rounds)
+    I->last_bounces = passes;
+    I->ring_bounces[slot] = tm ? passes : 0;
+    I->ring_nee[slot] = mode == RFW_HIP_RENDER_DEFAULT ? nee : ao;
+    I->ao_rounds = ao_rounds;
     I->frame_index++;
     if (I->frame_index - I->drained_index > kTimingRing) I->drained_index = I->frame_index - kTimingRing;
     I->frame_recorded = tm;
@@ -572,13 +630,14 @@ const char* rfw_hip_last_error(void* inst)
 }
 
 
-static int render_impl(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool samples = false)
+static int render_impl(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool samples = false, uint32_t mode = RFW_HIP_RENDER_DEFAULT)
 {
-    if (I->slots.empty()) return do_render(I, views, k, samples);
+    if (I->slots.empty()) return do_render(I, views, k, samples, mode);
     // frames in flight: does this call add a sample to the image of the current slot, or start a new image on the next slot?
     Instance* cur = slot_ptr(I, I->cur_slot);
     const bool same_image = (k == 1 || samples) && !I->restart && cur->sample_count > 0 && cur->have_last_view &&
-                            std::memcmp(&cur->last_view, views, sizeof(*views)) == 0 && cur->rendered_version == I->scene_version;
+                            std::memcmp(&cur->last_view, views, sizeof(*views)) == 0 && cur->rendered_version == I->scene_version &&
+                            cur->render_mode == mode;
     if (!same_image) {
         I->cur_slot = (I->cur_slot + 1) % (uint32_t)(I->slots.size() + 1);
         cur = slot_ptr(I, I->cur_slot);
@@ -589,19 +648,21 @@ static int render_impl(Instance* I, const rfw_camera_view_3d* views, uint32_t k,
     if (cur != I) { // the owner's options apply to every slot
         cur->max_path_length = I->max_path_length; cur->clamp_value = I->clamp_value; cur->flags = I->flags; cur->timing = I->timing;
         for (int c = 0; c < 3; c++) cur->sky[c] = I->sky[c];
+        cur->ao_samples = I->ao_samples; cur->ao_radius = I->ao_radius;
     }
     int rc = ensure_slot_tlas(I, cur);
-    if (rc == RFW_HIP_OK) rc = do_render(cur, views, k, samples);
+    if (rc == RFW_HIP_OK) rc = do_render(cur, views, k, samples, mode);
     if (rc != RFW_HIP_OK && cur != I && !cur->err.empty()) I->err = cur->err;
     return rc;
 }
 
-int rfw_hip_render(void* inst, const rfw_mat4* /*view_2d*/, const rfw_camera_view_3d* view, uint32_t /*mode*/)
+int rfw_hip_render(void* inst, const rfw_mat4* /*view_2d*/, const rfw_camera_view_3d* view, uint32_t mode)
 {
     LOCK(inst);
     if (!view) return fail(I, RFW_HIP_E_INVALID, "render: null view");
     CHECK_OVERFLOW(I); // of an earlier frame or query (sticky until synchronize() rebuilds the trees)
-    return render_impl(I, view, 1);
+    // unknown values render as DEFAULT (the wgpu backend shows its default output for them too)
+    return render_impl(I, view, 1, false, mode <= (uint32_t)RFW_HIP_RENDER_FILTERED_SSAO ? mode : (uint32_t)RFW_HIP_RENDER_DEFAULT);
 }
 
 int rfw_hip_render_batch(void* inst, const rfw_camera_view_3d* views, uint32_t count)
@@ -699,6 +760,17 @@ int rfw_hip_set_option(void* inst, const char* key, double value)
     }
     else if (k == "tlas_fused") I->tlas_fused = std::max(0, std::min(2, (int)value)); // 0: always the launch chain (lbvh_build); 1: always the one-workgroup build (up to 16 384 instances); 2: that where frames overlap (frame slots)
     else if (k == "sample_count") I->sample_count = (uint32_t)value;
+    else if (k == "ao_samples" || k == "ao_radius") { // render modes 5, 6: a new image
+        if (k == "ao_samples") {
+            if (!(value >= 1.0 && value <= (double)kAoMaxSamples)) return fail(I, RFW_HIP_E_INVALID, "set_option: ao_samples is 1 ... 8");
+            I->ao_samples = (uint32_t)value;
+        } else {
+            if (!(value >= 0.0) || !std::isfinite(value)) return fail(I, RFW_HIP_E_INVALID, "set_option: ao_radius is >= 0 (0 = automatic)");
+            I->ao_radius = (float)value;
+        }
+        I->sample_count = 0;
+        I->restart = true;
+    }
     else if (k == "gather_format") { // 0 f32 accumulator RGB, 1 f16 finished frame, 2 presented BGRA8 (sharded frames only)
         if (value < 0 || value > 2) return fail(I, RFW_HIP_E_INVALID, "set_option: gather_format is 0, 1 or 2");
         I->gather_format = (uint32_t)value;

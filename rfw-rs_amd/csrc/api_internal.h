@@ -468,6 +468,15 @@ struct Instance {
     uint32_t sample_count = 0;
     bool have_last_view = false;
     rfw_camera_view_3d last_view{};
+    // render modes (rfw_hip_render's `mode`, aov.inc): the mode of the image this slot accumulates (0 = path traced; a change starts a new
+    // image), the options of the ambient occlusion modes, the filter guide of the latest AO frame, and how many AO rounds it traced
+    uint32_t render_mode = 0;
+    uint32_t ao_samples = 4;
+    float ao_radius = 0.0f;            // 0 = automatic: 5 % of the diagonal of the scene's bounds (ao_auto_radius)
+    float ao_auto_radius = 0.0f;       // owner: resolved for scene version ao_auto_version, at the first AO frame after a synchronize()
+    uint64_t ao_auto_version = 0;
+    uint32_t ao_rounds = 0;            // per slot: AO rounds of the latest frame (0: it traced none, "ao_rays" is empty)
+    DevBuf<float4> d_ao_guide;         // per slot: width x height (faced gN, t), written by k_aov in modes 5 and 6
     std::vector<hipEvent_t> ring;  // [kTimingRing][substreams][kNumEvents]
     hipEvent_t* events = nullptr;   // event set of the current frame, sub-shard 0
     uint32_t substreams = 1;        // the frame's tiles are dealt to this many sub-shards, each traced on its own stream
@@ -563,7 +572,7 @@ int alloc_paths(Instance* I);
 SceneDev scene_dev(Instance* I);
 CameraParams camera_params(const Instance* I, const rfw_camera_view_3d& v, uint32_t sub = 0);
 PathDev path_dev(Instance* I, uint32_t sub = 0);
-int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k = 1, bool samples = false);
+int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k = 1, bool samples = false, uint32_t mode = 0); // mode: RFW_HIP_RENDER_*, 0 for k > 1
 uint32_t spill_stride(const Instance* I);
 bool blas_wide_wanted(const Instance* I, uint64_t n_prims); // api_scene.cpp: does a packet kernel run on a scene of this size under the current options?
 uint32_t index_magic(uint32_t d, uint64_t n_max); // api_frame.cpp: reciprocal for the kernels' index divisions (0: none exact far enough)

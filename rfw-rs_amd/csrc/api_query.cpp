@@ -237,7 +237,7 @@ int rfw_hip_debug_lbvh_stress(void* inst, uint32_t n, uint32_t iterations, uint3
 }
 
 // what: "hit0"/"hit1" (uint4), "ray_o0"/"ray_o1", "ray_d0"/"ray_d1", "thr0"/"thr1", "sh_o", "sh_d", "sh_e" (float4), "counters",
-//       "xforms" (InstanceXform), "normals" (InstanceNormal)
+//       "xforms" (InstanceXform), "normals" (InstanceNormal), "ao_rays", "ao_guide" (render modes 5, 6: DESIGN.md "Render modes")
 int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, uint64_t* written)
 {
     LOCK(inst);
@@ -259,6 +259,40 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
         if (rc != RFW_HIP_OK) I->err = c->err;
         return rc;
     }
+    if (w == "ao_rays") { // the last AO round of the latest frame: 32 B per ray (origin xyz, t_max, direction xyz, frame pixel), by pixel; t_min = 1e-3
+        HIP_TRY(I, hipStreamSynchronize(I->stream));
+        std::vector<uint32_t> rays;
+        if (I->ao_rounds) {
+            const size_t n = I->cap_v;
+            std::vector<float4> o(n), d(n);
+            for (uint32_t s = 0; s < I->substreams; s++) { // sub-shard s: its queue at s * cap_v * kShadowBuckets, round r in bucket r
+                const size_t at = ((size_t)s * kShadowBuckets + (I->ao_rounds - 1u)) * n;
+                HIP_TRY(I, hipMemcpy(o.data(), I->d_sh_o.ptr + at, n * sizeof(float4), hipMemcpyDeviceToHost));
+                HIP_TRY(I, hipMemcpy(d.data(), I->d_sh_d.ptr + at, n * sizeof(float4), hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < n; i++) {
+                    uint32_t px;
+                    std::memcpy(&px, &o[i].w, 4);
+                    if (px == 0xffffffffu) continue; // no ray (a miss, or no pixel)
+                    const float t_max = d[i].w - 0.0001f; // what k_shadow traces to
+                    const float e[8] = {o[i].x, o[i].y, o[i].z, t_max, d[i].x, d[i].y, d[i].z, 0.0f};
+                    const size_t k = rays.size();
+                    rays.resize(k + 8);
+                    std::memcpy(rays.data() + k, e, sizeof(e));
+                    rays[k + 7] = px;
+                }
+            }
+            std::vector<size_t> order(rays.size() / 8);
+            for (size_t i = 0; i < order.size(); i++) order[i] = i;
+            std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return rays[8 * a + 7] < rays[8 * b + 7]; });
+            std::vector<uint32_t> sorted(rays.size());
+            for (size_t i = 0; i < order.size(); i++) std::memcpy(sorted.data() + 8 * i, rays.data() + 8 * order[i], 32);
+            rays.swap(sorted);
+        }
+        const uint64_t n = std::min<uint64_t>(bytes, rays.size() * 4);
+        if (n) std::memcpy(dst, rays.data(), n);
+        if (written) *written = n;
+        return RFW_HIP_OK;
+    }
     const void* src = nullptr;
     uint64_t avail = 0;
     const uint64_t q = (uint64_t)I->capacity * 16;
@@ -273,6 +307,7 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
     else if (w == "sh_o") { src = I->d_sh_o.ptr; avail = q * kShadowBuckets; } // bucket b at element b * capacity
     else if (w == "sh_d") { src = I->d_sh_d.ptr; avail = q * kShadowBuckets; } // bucket b at element b * capacity
     else if (w == "sh_e") { src = I->d_sh_e.ptr; avail = q * kShadowBuckets; } // bucket b at element b * capacity
+    else if (w == "ao_guide") { src = I->d_ao_guide.ptr; avail = (uint64_t)std::min<size_t>((size_t)I->width * I->height, I->d_ao_guide.cap) * 16; } // (faced gN, t) per frame pixel of the latest AO frame; t = 0: the camera ray missed
     else if (w == "counters") { src = I->d_counters.ptr + (size_t)I->counter_phase * kMaxSub; avail = sizeof(QueueCounters); }
     else if (w == "tlas_raw") { src = I->d_tlas_raw.ptr; avail = (uint64_t)I->d_tlas_raw.cap * sizeof(Node4); }         // the device-built TLAS before quantisation (entries past the node count are stale)
     else if (w == "tlas_nodes") { src = I->d_tlas_nodes.ptr; avail = (uint64_t)I->d_tlas_nodes.cap * sizeof(Node4Q); }

@@ -89,12 +89,13 @@ void launch_tlas_finish(hipStream_t s, const Node4* raw, Node4Q* out, const Octa
 void launch_expand_nodes(hipStream_t s, const Node4Q* in, const OctantCopies& oc, uint32_t first, uint32_t n, const uint32_t* live = nullptr); // the copies of already quantised nodes
 // the same for slots [0, n) holding SEVERAL trees: record k's tree lives at recs[k].node_base and has counts[k] nodes (both on the device)
 void launch_quantize_regions(hipStream_t s, const Node4* in, Node4Q* out, const OctantCopies& oc, uint32_t n, const MeshRecord* recs, const uint32_t* counts, uint32_t n_recs);
+// linear: render modes 1-6 finalise as acc / samples instead of sqrt(acc / samples) (the accumulator read is the same either way)
 void launch_assemble(hipStream_t s, const CameraParams& cam, const void* gathered, bool rgb, bool accumulator, uint64_t slab_elems, float4* frame,
-                     uint32_t samples);
+                     uint32_t samples, bool linear = false);
 void launch_sum_batch(hipStream_t s, float4* acc_slabs, uint64_t slab_elems, uint32_t count); // slab 0 += slabs 1 .. count - 1, in order
 void launch_pack_rgb(hipStream_t s, const float4* acc_slab, float* out, uint64_t n);
 // the FINISHED frame of a slab for the all-gather (format 1: three halves per pixel; 2: presented B, G, R, A bytes) and its de-tiling
-void launch_pack_finished(hipStream_t s, const float4* acc_slab, void* out, uint64_t n, uint32_t samples, uint32_t format, const float* steps255);
+void launch_pack_finished(hipStream_t s, const float4* acc_slab, void* out, uint64_t n, uint32_t samples, uint32_t format, const float* steps255, bool linear = false);
 // peer-to-peer exchange: flag words in uncached memory.  wait: lanes first .. first + count - 1 of ONE wavefront poll flags[lane] until it has
 // reached `want` (wrap-safe), at most `limit_ticks` of the 100 MHz wall clock, then *timeout_flag = 1.  signal: *targets.p[i] = value.
 struct P2PTargets { uint32_t* p[16]; };
@@ -102,6 +103,13 @@ void launch_p2p_wait(hipStream_t s, const uint32_t* flags, uint32_t first, uint3
 void launch_p2p_signal(hipStream_t s, const P2PTargets& targets, uint32_t count, uint32_t value);
 void launch_assemble_finished(hipStream_t s, const CameraParams& cam, const void* gathered, uint64_t slab_elems, uint32_t format, float4* frame, uint32_t* presented);
 void launch_present(hipStream_t s, const float4* frame, uint32_t* bgra, uint64_t n, const float* steps255, bool narrow);
+constexpr uint32_t kAoMaxSamples = kShadowBuckets; // AO rays per pixel and sample: round r goes through shadow bucket r
+// render modes 1-6 (aov.inc): after the primary launch, the mode's value into the accumulator slab (1-4), or the ambient occlusion rays of
+// rounds 0 .. ao_samples - 1 into shadow buckets 0 .. ao_samples - 1 and the filter guide (5, 6); `direction` = the view's (mode 4)
+void launch_aov(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, uint32_t mode, uint32_t ao_samples, float ao_radius, float4* guide,
+                const float direction[3]);
+// mode 6 where the frame is de-tiled on this device: the edge-aware filter of acc.x / samples (slabs of slab_elems, as launch_assemble) into `frame`
+void launch_ao_filter(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, float4* frame, uint32_t samples);
 void launch_eval_shading(hipStream_t s, const SceneDev& sc, const CameraParams& cam, int op, uint32_t n, const float* in, float* out);
 void launch_query_closest(hipStream_t s, const SceneDev& sc, const float* origins, const float* directions, float t_min, float t_max, uint64_t n,
                           rfw_hip_hit* hits, uint32_t* depth = nullptr /* optional: nodes visited per ray */);

@@ -985,15 +985,18 @@ __global__ __launch_bounds__(256) void k_pack_rgb(const float4* __restrict__ acc
 }
 // What a rank contributes to the all-gather when only the FINISHED frame has to travel (option "gather_format"; the accumulators stay on
 // the rank that owns the tiles, where the next sample is added): blit.comp's sqrt(acc / samples) as three halves (6 B per pixel) ...
+// (LINEAR: render modes 1-6 finalise as the plain mean acc / samples, aov.inc; the path tracer's instantiation is the one without it)
+template <bool LINEAR> RFW_DI float finalise(const float a, const float s) { return LINEAR ? a * 1.0f / s : __builtin_sqrtf(a * 1.0f / s); }
+template <bool LINEAR>
 __global__ __launch_bounds__(256) void k_pack_f16(const float4* __restrict__ acc_slab, _Float16* __restrict__ out, const uint64_t n, const uint32_t samples)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const float4 a = acc_slab[i];
     const float s = (float)(int)samples;
-    out[3 * i] = (_Float16)__builtin_sqrtf(a.x * 1.0f / s);
-    out[3 * i + 1] = (_Float16)__builtin_sqrtf(a.y * 1.0f / s);
-    out[3 * i + 2] = (_Float16)__builtin_sqrtf(a.z * 1.0f / s);
+    out[3 * i] = (_Float16)finalise<LINEAR>(a.x, s);
+    out[3 * i + 1] = (_Float16)finalise<LINEAR>(a.y, s);
+    out[3 * i + 2] = (_Float16)finalise<LINEAR>(a.z, s);
 }
 // ... or as the swap-chain image itself, B, G, R, A bytes (4 B per pixel): exactly what k_present makes of the de-tiled frame
 struct SrgbSteps { float t[256]; };
@@ -1004,6 +1007,7 @@ __device__ inline uint32_t srgb_encode(const float* s_t, float x)
         if (x >= s_t[lo + bit - 1]) lo += bit;
     return lo;
 }
+template <bool LINEAR>
 __global__ __launch_bounds__(256) void k_pack_bgra8(const float4* __restrict__ acc_slab, uint32_t* __restrict__ out, const uint64_t n, const uint32_t samples,
                                                    const SrgbSteps steps)
 {
@@ -1013,7 +1017,7 @@ __global__ __launch_bounds__(256) void k_pack_bgra8(const float4* __restrict__ a
     const float s = (float)(int)samples;
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
         const float4 a = acc_slab[i];
-        const float r = __builtin_sqrtf(a.x * 1.0f / s), g = __builtin_sqrtf(a.y * 1.0f / s), b = __builtin_sqrtf(a.z * 1.0f / s);
+        const float r = finalise<LINEAR>(a.x, s), g = finalise<LINEAR>(a.y, s), b = finalise<LINEAR>(a.z, s);
         out[i] = srgb_encode(s_t, b) | (srgb_encode(s_t, g) << 8) | (srgb_encode(s_t, r) << 16) | 0xff000000u;
     }
 }
@@ -1067,8 +1071,9 @@ __global__ __launch_bounds__(256) void k_present(const float4* __restrict__ fram
 // all-gathered slabs [world][slab_elems] -> full frame.  RGB: the gathered buffer holds 3 floats per element (k_pack_rgb), else the
 // instance's own float4 slab (world == 1)
 // ACC = false: the finalised frame (blit.comp: sqrt(acc / samples)) — what every frame needs; ACC = true: the linear accumulator itself,
-// produced only when somebody asks for it (rfw_hip_read_accumulator): a third of the de-tiling traffic of every frame otherwise
-template <bool RGB, bool ACC>
+// produced only when somebody asks for it (rfw_hip_read_accumulator): a third of the de-tiling traffic of every frame otherwise.
+// LINEAR (render modes 1-6): the finalised frame is acc / samples, no sqrt
+template <bool RGB, bool ACC, bool LINEAR = false>
 __global__ void k_assemble(const CameraParams cam, const void* __restrict__ gathered_v, const uint64_t slab_elems, float4* __restrict__ frame,
                            const uint32_t samples)
 {
@@ -1090,8 +1095,7 @@ __global__ void k_assemble(const CameraParams cam, const void* __restrict__ gath
         frame[px + py * cam.width] = a;
     } else {
         const float n = (float)(int)samples;
-        frame[px + py * cam.width] = make_float4(__builtin_sqrtf(a.x * 1.0f / n), __builtin_sqrtf(a.y * 1.0f / n), __builtin_sqrtf(a.z * 1.0f / n),
-                                                 __builtin_sqrtf(a.w * 1.0f / n));
+        frame[px + py * cam.width] = make_float4(finalise<LINEAR>(a.x, n), finalise<LINEAR>(a.y, n), finalise<LINEAR>(a.z, n), finalise<LINEAR>(a.w, n));
     }
 }
 
@@ -1445,10 +1449,13 @@ void launch_quantize_regions(hipStream_t s, const Node4* in, Node4Q* out, const 
     if (oc.quant) hipLaunchKernelGGL(k_expand_regions, dim3(ceil_div((uint64_t)n * 8u, 256)), dim3(256), 0, s, out, oc.wide, oc.quant, oc.stride, n, recs, counts, n_recs);
 }
 void launch_assemble(hipStream_t s, const CameraParams& cam, const void* gathered, bool rgb, bool accumulator, uint64_t slab_elems, float4* frame,
-                     uint32_t samples)
+                     uint32_t samples, bool linear)
 {
     const dim3 block(16, 4), grid(ceil_div(cam.width, 16), ceil_div(cam.height, 4), cam.batch > 1 ? cam.batch : 1u);
-    if (rgb && accumulator) hipLaunchKernelGGL((k_assemble<true, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
+    if (linear && !accumulator) {
+        if (rgb) hipLaunchKernelGGL((k_assemble<true, false, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
+        else hipLaunchKernelGGL((k_assemble<false, false, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
+    } else if (rgb && accumulator) hipLaunchKernelGGL((k_assemble<true, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
     else if (rgb) hipLaunchKernelGGL((k_assemble<true, false>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
     else if (accumulator) hipLaunchKernelGGL((k_assemble<false, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
     else hipLaunchKernelGGL((k_assemble<false, false>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
@@ -1464,11 +1471,14 @@ void launch_sum_batch(hipStream_t s, float4* acc_slabs, uint64_t slab_elems, uin
 {
     if (slab_elems && count > 1) hipLaunchKernelGGL(k_sum_batch, dim3((unsigned)ceil_div(slab_elems, 256)), dim3(256), 0, s, acc_slabs, slab_elems, count);
 }
-void launch_pack_finished(hipStream_t s, const float4* acc_slab, void* out, uint64_t n, uint32_t samples, uint32_t format, const float* steps255)
+void launch_pack_finished(hipStream_t s, const float4* acc_slab, void* out, uint64_t n, uint32_t samples, uint32_t format, const float* steps255, bool linear)
 {
     if (!n) return;
-    if (format == 1) hipLaunchKernelGGL(k_pack_f16, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, acc_slab, (_Float16*)out, n, samples);
-    else hipLaunchKernelGGL(k_pack_bgra8, dim3((unsigned)std::min<uint64_t>(ceil_div(n, 256), 8192)), dim3(256), 0, s, acc_slab, (uint32_t*)out, n, samples, make_steps(steps255));
+    const dim3 g16((unsigned)ceil_div(n, 256)), g8((unsigned)std::min<uint64_t>(ceil_div(n, 256), 8192));
+    if (format == 1 && linear) hipLaunchKernelGGL(k_pack_f16<true>, g16, dim3(256), 0, s, acc_slab, (_Float16*)out, n, samples);
+    else if (format == 1) hipLaunchKernelGGL(k_pack_f16<false>, g16, dim3(256), 0, s, acc_slab, (_Float16*)out, n, samples);
+    else if (linear) hipLaunchKernelGGL(k_pack_bgra8<true>, g8, dim3(256), 0, s, acc_slab, (uint32_t*)out, n, samples, make_steps(steps255));
+    else hipLaunchKernelGGL(k_pack_bgra8<false>, g8, dim3(256), 0, s, acc_slab, (uint32_t*)out, n, samples, make_steps(steps255));
 }
 void launch_assemble_finished(hipStream_t s, const CameraParams& cam, const void* gathered, uint64_t slab_elems, uint32_t format, float4* frame, uint32_t* presented)
 {
@@ -1576,5 +1586,8 @@ void launch_query_any(hipStream_t s, const SceneDev& sc, const float* origins, c
     if (depth) hipLaunchKernelGGL(k_query_any<true>, dim3(ceil_div(n, kTraceBlock)), dim3(kTraceBlock), 0, s, sc, origins, directions, t_min, t_max, n, occluded, depth);
     else hipLaunchKernelGGL(k_query_any<false>, dim3(ceil_div(n, kTraceBlock)), dim3(kTraceBlock), 0, s, sc, origins, directions, t_min, t_max, n, occluded, depth);
 }
+
+// ---------------------------------------------------------------- render modes 1-6 (rfw_hip_render's `mode`)
+#include "aov.inc"
 
 } // namespace rfwhip
