@@ -6,15 +6,22 @@ BASELINE.json north_star; SURVEY.md §8d C4 geometry, primary + shadow rays), ev
 
 N = 1: `value` is what a client of the reference's plugin trait gets — ONE `Backend::render` call per frame and nothing else
 (rfw_hip_render; 12 frame slots inside the instance keep frames in flight because every frame has its own camera view, a slow dolly,
-so each call starts a new image).  Two further modes are measured after the timed region and reported beside it (`config.modes`):
-strictly one frame at a time, and frames traced 8 per launch through the rfw_hip_render_batch extension.  The first and the last
-frame of the timed region are read back and compared, bit for bit, with the CPU oracle's frames of the same views at the same
-resolution (`config.timed_frame_equals_oracle`); the oracle's time for those frames is the `cpu_baseline`.
+so each call starts a new image).
 
 N > 1: the frame is sharded by 64x64 tiles across ranks; `value` is north_star's protocol — one render() and ONE all-gather of the
-framebuffer per frame (RCCL over xGMI; strong scaling: the frame is fixed), 8 (N = 2) or 12 renderer instances in flight.  Batches of 8
-frames traced per launch with one exchange per batch (the rfw_hip_render_batch extension) are measured after the timed region and reported
-as a row of config.modes."""
+framebuffer per frame (RCCL over xGMI; strong scaling: the frame is fixed), 8 (N = 2) or 12 renderer instances in flight.
+
+A plain run does what the result line's `value` needs and nothing more: it builds the scene, counts the rays of every view, warms up,
+times the steps, writes --dump-outputs if asked and prints the line.  `--full` adds everything else, after the timed region unless said
+otherwise:
+  * N = 1: BASELINE.json's other single-GPU configurations as child runs before this process touches the GPU (config.modes), the warm
+    acceleration-structure rebuild before the warm-up (config.bvh.build), further modes — strictly one frame at a time, 8 frame slots,
+    frames traced 8 per launch through the rfw_hip_render_batch extension (config.modes) — with their per-kernel durations, the in-job
+    bandwidth and issue probes and the roofline built on them, and the CPU oracle: the first and the last frame of the timed region
+    compared, bit for bit, with the oracle's frames of the same views at the same resolution (config.timed_frame_equals_oracle), the
+    oracle's time for those frames being the `cpu_baseline`;
+  * N > 1: batches of 8 frames traced per launch with one exchange per batch (a row of config.modes), and rank 0's check that the sharded
+    frames equal the frames one GPU renders alone (config.sharded_frame_equals_single_gpu_frame)."""
 import argparse
 import contextlib
 import ctypes
@@ -157,8 +164,13 @@ def main():
     ap.add_argument("--procedural", action="store_true",
                     help="hand the generated scene to the backend directly; default: write it as a binary glTF 2.0 file (host/gltf_export.cpp) and "
                          "run on what the glTF importer (host/gltf.cpp) reads back — the configurations of BASELINE.json are glTF scenes")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle leg (CPU baseline + check of the timed frames)")
-    ap.add_argument("--no-modes", action="store_true", help="skip the secondary modes (one frame at a time / batches) after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else the bench reports (module docstring): other configurations, modes, "
+                         "per-kernel durations, probes and roofline, the CPU oracle; the --no-* options below leave parts of that out")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="skip the oracle leg (CPU baseline + check of the timed frames; --full) and the copy of the first timed frame it reads, "
+                         "which is made inside the timed region in every run without this option")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip the secondary modes (one frame at a time / batches) after the timed region")
     ap.add_argument("--separate-spheres", action="store_true", help="atrium1m: C4's 64 displaced icospheres as 64 meshes with one instance each (65 meshes, SURVEY §8d literally) instead of one baked mesh")
     ap.add_argument("--identical-frames", action="store_true", help="every frame the same view (round 1's configuration; frames then share every cache line)")
     ap.add_argument("--emulate-shard", type=int, default=0,
@@ -174,12 +186,12 @@ def main():
     ap.add_argument("--present-rank", type=int, default=0, help="N > 1: the rank that de-tiles every gathered frame at once (-1: all ranks do)")
     ap.add_argument("--readback", nargs="?", const="float", default=None, choices=["float", "presented"],
                     help="copy every finished frame to (pinned) host memory inside the timed region (the PCIe-inclusive rate of DESIGN.md; never the headline)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--mode-frames", type=int, default=48, help="frames per secondary mode")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: seconds of CPU rendering for the oracle's cpu_baseline")
+    ap.add_argument("--mode-frames", type=int, default=48, help="--full: frames per secondary mode")
     ap.add_argument("--no-baseline-configs", action="store_true",
-                    help="the headline run (atrium1m, max path length 1, one GPU) also runs BASELINE.json's other single-GPU configurations — C2, C3 and the "
-                         "path-traced C4 — as short child runs of this script, each with its own oracle check, and reports them in config.modes; this skips them")
-    ap.add_argument("--baseline-steps", type=int, default=200, help="timed frames of each of those child runs")
+                    help="a --full headline run (atrium1m, max path length 1, one GPU) also runs BASELINE.json's other single-GPU configurations — C2, C3 and the "
+                         "path-traced C4 — as short --full child runs of this script, each with its own oracle check, and reports them in config.modes; this skips them")
+    ap.add_argument("--baseline-steps", type=int, default=200, help="--full: timed frames of each of those child runs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: the frame's accumulator "
                          "and a fixed, seeded sample of its finished framebuffer (float32; the sample's pixel indices float64; at most 64 MB in all); the inputs are the same from run to run")
@@ -209,8 +221,8 @@ def main():
     # process beside one that holds its 16 hardware queues — even idle ones — oversubscribes the device's queues and runs 5-13 % slower
     # (measured: C3 as a child of an initialised parent 5690, alone 6568 Mrays/s on the same box)
     baseline_rows = {}
-    if (world == 1 and not args.emulate_shard and not args.no_baseline_configs and not args.no_modes and not args.rendezvous_only and args.workload == "atrium1m"
-            and args.max_path_length == 1 and (args.width, args.height) == (1920, 1080) and not args.identical_frames and not args.readback):
+    if (args.full and world == 1 and not args.emulate_shard and not args.no_baseline_configs and not args.no_modes and not args.rendezvous_only
+            and args.workload == "atrium1m" and args.max_path_length == 1 and (args.width, args.height) == (1920, 1080) and not args.identical_frames and not args.readback):
         baseline_rows = baseline_configs(args)
 
     import numpy as np
@@ -345,7 +357,7 @@ def main():
     torch.cuda.synchronize()
     # the acceleration-structure build, warm: everything changed -> synchronize(), three times; the device's share by events
     build_report = None
-    if rank == 0 and single and not animated:
+    if args.full and rank == 0 and single and not animated:
         warm = []
         for _ in range(3):
             scene.mark_all_changed()
@@ -480,7 +492,8 @@ def main():
             state["pending"] = []
 
     # frame 0 of the timed region is copied out (asynchronously, behind its kernels, into pinned memory) for the oracle check; the buffer is
-    # allocated here, before the warm-up, so that nothing but the synchronisation sits between the warm-up and the timed region
+    # allocated here, before the warm-up, so that nothing but the synchronisation sits between the warm-up and the timed region.  The copy
+    # is made whether or not --full then checks it, so that a plain and a --full run time the same steps
     check0 = bes[0].host_frame() if (single and rank == 0 and not args.no_cpu_baseline and B == 1) else None
     for i in range(args.warmup):
         step(i)
@@ -518,12 +531,13 @@ def main():
     timed_frames_gpu = None
     if check0 is not None:
         bes[0].wait_downloads()
-        lb, lframes = state["last"]
-        timed_frames_gpu = [(0, np.array(check0, copy=True)), (lframes[-1], lb.accumulator())]
+        if args.full:
+            lb, lframes = state["last"]
+            timed_frames_gpu = [(0, np.array(check0, copy=True)), (lframes[-1], lb.accumulator())]
     dumped = dump_outputs(args.dump_outputs, state["last"]) if (args.dump_outputs and rank == 0) else None
     # Sharded frame: is what the all-gather + assemble left on this rank the frame one GPU renders alone?  (static scenes only)
     shard_check = None
-    if world > 1 and rank == 0 and not animated and state["last"] is not None:
+    if args.full and world > 1 and rank == 0 and not animated and state["last"] is not None:
         lb, lframes = state["last"]
         whole = HipBackend.init(w, h, 1.0, device=dev, max_path_length=args.max_path_length)
         scene.mark_all_changed()
@@ -551,7 +565,7 @@ def main():
     # ---- N > 1: the same frames in batches of 8 — ONE exchange per batch instead of one per frame — as a secondary mode (north_star's protocol,
     # one exchange per frame, is the `value` above)
     batch_mode = None
-    if world > 1 and B == 1 and not args.no_modes and not animated and not args.emulate_shard and not args.readback:
+    if args.full and world > 1 and B == 1 and not args.no_modes and not animated and not args.emulate_shard and not args.readback:
         for b_ in bes:
             b_.close()
         headline_setup = (B, F, use_slots)
@@ -587,7 +601,7 @@ def main():
     # host cost of the per-frame scene update (animate + set_3d_instances + synchronize) without back-pressure
     host_sync_ms = None
     host_render_ms = None
-    if animated:
+    if animated and args.full:
         acc_t = acc_r = 0.0
         for i in range(20):
             torch.cuda.synchronize()
@@ -616,7 +630,7 @@ def main():
             modes[headline_mode]["exchanges"] = args.steps  # one per frame
         if batch_mode:
             modes["render_batch of 8, 3 batches in flight: one exchange per batch (extension call)"] = batch_mode
-    if single and not args.no_modes and not animated:
+    if args.full and single and not args.no_modes and not animated:
         if F == 1 and B == 1:
             iso = bes[0].drain_timing()  # the timed region itself was one frame at a time: its own per-kernel events
         for b_, _, _ in inst:
@@ -664,10 +678,10 @@ def main():
             modes["render_batch of 8, 3 frame slots (extension call)"] = run_mode(3, 8, nf_mode - nf_mode % 8, False)[0]
         if args.max_path_length > 1:
             modes["render_samples: 4 spp of one image per call, 3 frame slots (extension call)"] = run_mode(3, 1, max(nf_mode // 4, 8), False, spp=4)[0]
-    elif F == 1 and B == 1 and single:
+    elif args.full and F == 1 and B == 1 and single:
         ms, n = bes[0].drain_timing()
         iso = (ms, n)
-    elif single:
+    elif args.full and single:
         # no separate strict mode requested: a short one-frame-at-a-time pass on the instance at hand gives the per-kernel durations
         # (C3: with its scene update before every frame, as in the timed region)
         bes[0].set_option("timing", 1)
@@ -682,7 +696,7 @@ def main():
 
     # this job's own HBM roofline: a float4 device copy, measured after the timed region
     bw_measured = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             pb = bes[0] if bes else HipBackend.init(64, 64, 1.0, device=dev)
             bw_measured = pb.bandwidth_probe(1 << 30, 20)
@@ -696,50 +710,52 @@ def main():
 
     if rank == 0:
         node_b, tri_b = sstats["node_bytes"], sstats["tri_bytes"]
-        nv = len(per_view)
-        mean = lambda key, k=None: sum((s[key][k] if k is not None else s[key]) for s in per_view) / nv
-        n_prim, n_shad = mean("primary_rays"), mean("shadow_rays")
-        # SURVEY §8(d)'s contract figure: ALGORITHMIC bytes per launch (mean over the views)
-        alg = {
-            # nodes x 64 B + triangles x 48 B + instance records x 64 B + 48 B written per ray (origin, direction, hit) + 16 B accumulator clear
-            "k_primary": mean("nodes_visited", 0) * node_b + mean("tris_tested", 0) * tri_b + mean("instances_entered", 0) * 64 + n_prim * (48 + 16),
-            # + 32 B queue entry read per ray, 16 B contribution read and 32 B accumulator read-modify-write per unoccluded ray (counted for all)
-            "k_shadow": mean("nodes_visited", 2) * node_b + mean("tris_tested", 2) * tri_b + mean("instances_entered", 2) * 64 + n_shad * (32 + 16 + 32),
-            # per path: hit 16 + ray 32 read; per hit: RTTriangle 176 + material 96 + normal matrix 48; shadow-queue push 48 per shadow ray
-            "k_shade": n_prim * (16 + 32) + n_prim * (176 + 96 + 48) + n_shad * 48,
-        }
-        n_ext = mean("extension_rays")
-        if n_ext:
-            # the extension rays of ALL bounces of a frame: 32 B of ray read and 16 B of hit record written per ray
-            alg["k_extend"] = mean("nodes_visited", 1) * node_b + mean("tris_tested", 1) * tri_b + mean("instances_entered", 1) * 64 + n_ext * (32 + 16)
-        kms = None
-        if iso and iso[1] > 0:
-            kms = {"k_primary": iso[0]["ms_trace_primary"] / iso[1], "k_shadow": iso[0]["ms_trace_shadow"] / iso[1], "k_shade": iso[0]["ms_shade"] / iso[1]}
-            if "k_extend" in alg:
-                kms["k_extend"] = iso[0]["ms_trace_extend"] / iso[1]
-            # launches of a kernel per frame: the ms above are sums over them, the counters of profiles/ are means per launch
-            # (shadow rays: bounce 0 is traced one ray per lane by k_shadow, the bounces by the streaming flavour k_shadow_stream)
-            launches = {"k_primary": 1, "k_shade": args.max_path_length, "k_shadow": 1, "k_shadow_stream": max(args.max_path_length - 1, 0),
-                        "k_extend": max(args.max_path_length - 1, 1)}
-        roofline = build_roofline(alg, kms, ms_step, sum(alg.values()), bw_measured, args, single, launches if kms else None)
-        if os.environ.get("RFW_PACKET_TRACE", "1") not in ("0", "2"):
-            # camera rays walk the tree as wavefront packets (csrc/traverse_packet.h): a node (128 B, the octant copy) and a triangle packet (48 B)
-            # are fetched ONCE per wavefront through the scalar cache — what the launch actually asks the memory system for, next to §8(d)'s
-            # per-ray figure above (which prices every ray's own visits at 64 B per node)
-            waves = max(n_prim / 64.0, 1.0)
-            roofline["primary_packets"] = {"node_steps_per_wavefront": round(mean("node_test_executions", 0) / waves, 2),
-                                           "triangle_steps_per_wavefront": round(mean("tri_test_executions", 0) / waves, 2),
-                                           "bytes_fetched_per_launch": int(mean("node_test_executions", 0) * 128 + mean("tri_test_executions", 0) * 48 + n_prim * (48 + 16))}
-        roofline["nodes_per_ray"] = {"primary": round(mean("nodes_visited", 0) / max(n_prim, 1), 2), "shadow": round(mean("nodes_visited", 2) / max(n_shad, 1), 2)}
-        roofline["tris_per_ray"] = {"primary": round(mean("tris_tested", 0) / max(n_prim, 1), 2), "shadow": round(mean("tris_tested", 2) / max(n_shad, 1), 2)}
-        # SIMD efficiency of the traversal, from the instrumented frames: active lanes / 64 per execution of the node test and of the
-        # triangle test, and what lanes that finished before their wavefront cost (nodes / (64 x max per wave))
-        roofline["lane_utilisation"] = {name: {"node_test": round(mean("nodes_visited", k) / max(64 * mean("node_test_executions", k), 1), 3),
-                                               "triangle_test": round(mean("tris_tested", k) / max(64 * mean("tri_test_executions", k), 1), 3),
-                                               "finished_lanes_bound": round(mean("nodes_visited", k) / max(64 * mean("wave_max_nodes", k), 1), 3),
-                                               # share of the wavefront-level node tests in which all active lanes visit ONE node
-                                               "wave_uniform_node_tests": round(mean("uniform_node_test_executions", k) / max(mean("node_test_executions", k), 1), 3)}
-                                        for k, name in ((0, "primary"), (1, "extension"), (2, "shadow")) if mean("node_test_executions", k)}
+        roofline = None
+        if args.full:  # (its per-kernel durations and probes are --full's runs)
+            nv = len(per_view)
+            mean = lambda key, k=None: sum((s[key][k] if k is not None else s[key]) for s in per_view) / nv
+            n_prim, n_shad = mean("primary_rays"), mean("shadow_rays")
+            # SURVEY §8(d)'s contract figure: ALGORITHMIC bytes per launch (mean over the views)
+            alg = {
+                # nodes x 64 B + triangles x 48 B + instance records x 64 B + 48 B written per ray (origin, direction, hit) + 16 B accumulator clear
+                "k_primary": mean("nodes_visited", 0) * node_b + mean("tris_tested", 0) * tri_b + mean("instances_entered", 0) * 64 + n_prim * (48 + 16),
+                # + 32 B queue entry read per ray, 16 B contribution read and 32 B accumulator read-modify-write per unoccluded ray (counted for all)
+                "k_shadow": mean("nodes_visited", 2) * node_b + mean("tris_tested", 2) * tri_b + mean("instances_entered", 2) * 64 + n_shad * (32 + 16 + 32),
+                # per path: hit 16 + ray 32 read; per hit: RTTriangle 176 + material 96 + normal matrix 48; shadow-queue push 48 per shadow ray
+                "k_shade": n_prim * (16 + 32) + n_prim * (176 + 96 + 48) + n_shad * 48,
+            }
+            n_ext = mean("extension_rays")
+            if n_ext:
+                # the extension rays of ALL bounces of a frame: 32 B of ray read and 16 B of hit record written per ray
+                alg["k_extend"] = mean("nodes_visited", 1) * node_b + mean("tris_tested", 1) * tri_b + mean("instances_entered", 1) * 64 + n_ext * (32 + 16)
+            kms = None
+            if iso and iso[1] > 0:
+                kms = {"k_primary": iso[0]["ms_trace_primary"] / iso[1], "k_shadow": iso[0]["ms_trace_shadow"] / iso[1], "k_shade": iso[0]["ms_shade"] / iso[1]}
+                if "k_extend" in alg:
+                    kms["k_extend"] = iso[0]["ms_trace_extend"] / iso[1]
+                # launches of a kernel per frame: the ms above are sums over them, the counters of profiles/ are means per launch
+                # (shadow rays: bounce 0 is traced one ray per lane by k_shadow, the bounces by the streaming flavour k_shadow_stream)
+                launches = {"k_primary": 1, "k_shade": args.max_path_length, "k_shadow": 1, "k_shadow_stream": max(args.max_path_length - 1, 0),
+                            "k_extend": max(args.max_path_length - 1, 1)}
+            roofline = build_roofline(alg, kms, ms_step, sum(alg.values()), bw_measured, args, single, launches if kms else None)
+            if os.environ.get("RFW_PACKET_TRACE", "1") not in ("0", "2"):
+                # camera rays walk the tree as wavefront packets (csrc/traverse_packet.h): a node (128 B, the octant copy) and a triangle packet (48 B)
+                # are fetched ONCE per wavefront through the scalar cache — what the launch actually asks the memory system for, next to §8(d)'s
+                # per-ray figure above (which prices every ray's own visits at 64 B per node)
+                waves = max(n_prim / 64.0, 1.0)
+                roofline["primary_packets"] = {"node_steps_per_wavefront": round(mean("node_test_executions", 0) / waves, 2),
+                                               "triangle_steps_per_wavefront": round(mean("tri_test_executions", 0) / waves, 2),
+                                               "bytes_fetched_per_launch": int(mean("node_test_executions", 0) * 128 + mean("tri_test_executions", 0) * 48 + n_prim * (48 + 16))}
+            roofline["nodes_per_ray"] = {"primary": round(mean("nodes_visited", 0) / max(n_prim, 1), 2), "shadow": round(mean("nodes_visited", 2) / max(n_shad, 1), 2)}
+            roofline["tris_per_ray"] = {"primary": round(mean("tris_tested", 0) / max(n_prim, 1), 2), "shadow": round(mean("tris_tested", 2) / max(n_shad, 1), 2)}
+            # SIMD efficiency of the traversal, from the instrumented frames: active lanes / 64 per execution of the node test and of the
+            # triangle test, and what lanes that finished before their wavefront cost (nodes / (64 x max per wave))
+            roofline["lane_utilisation"] = {name: {"node_test": round(mean("nodes_visited", k) / max(64 * mean("node_test_executions", k), 1), 3),
+                                                   "triangle_test": round(mean("tris_tested", k) / max(64 * mean("tri_test_executions", k), 1), 3),
+                                                   "finished_lanes_bound": round(mean("nodes_visited", k) / max(64 * mean("wave_max_nodes", k), 1), 3),
+                                                   # share of the wavefront-level node tests in which all active lanes visit ONE node
+                                                   "wave_uniform_node_tests": round(mean("uniform_node_test_executions", k) / max(mean("node_test_executions", k), 1), 3)}
+                                            for k, name in ((0, "primary"), (1, "extension"), (2, "shadow")) if mean("node_test_executions", k)}
         out = {
             "metric": "Mrays/s (primary+shadow, 1spp)", "value": round(value, 2), "unit": "Mrays/s", "n_gpus": ranks_rendered,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True,
@@ -752,7 +768,7 @@ def main():
                        "rays_per_frame": int(sum(rays_of_view_total) / len(rays_of_view_total)), "rays_timed": int(rays_total),
                        "frames_in_flight": F * B, "batches_in_flight": F, "frames_per_batch": B,
                        "frames_in_flight_held_by": "frame slots of one instance (one scene copy)" if use_slots else (f"{F} renderer instances" if F > 1 else "-"),
-                       "modes": modes,
+                       "modes": modes, "full": args.full,
                        "readback_every_frame": args.readback or False, "sharded_frame_equals_single_gpu_frame": shard_check,
                        "ranks_seen": ranks_seen, "ranks_rendered": ranks_rendered, "distinct_devices": distinct_devices, "ranks": ranks_report,
                        "launched_by": ("bench.py itself (--gpus N without a launcher: N child processes)" if os.environ.get("RFW_BENCH_LAUNCHED_BY") else
@@ -769,12 +785,12 @@ def main():
                                "packet_copies": bool(sstats.get("packet_copies"))},
                        "synchronize_s": round(sync_s, 2), "max_path_length": args.max_path_length,
                        "instances": sstats["instances"], "tlas_nodes": sstats["tlas_nodes"],
-                       "per_frame_synchronize_ms": round(host_sync_ms, 3) if animated else None,
-                       "per_frame_render_call_ms": round(host_render_ms, 3) if animated else None,
+                       "per_frame_synchronize_ms": round(host_sync_ms, 3) if host_sync_ms is not None else None,
+                       "per_frame_render_call_ms": round(host_render_ms, 3) if host_render_ms is not None else None,
                        "per_frame_synchronize_wall_ms_in_timed_region": round(sync_ms[0] / args.steps, 3) if animated else None},
             "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only: the contract's CPU leg)
+        if args.full and not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only: the contract's CPU leg)
             check = []
             if timed_frames_gpu is not None:
                 check = [(views[vi % N_VIEWS], (frame0_time + k_ * (args.steps - 1)) if animated else None) for k_, (vi, _) in enumerate(timed_frames_gpu)]
@@ -834,7 +850,8 @@ def baseline_configs(args):
     """BASELINE.json's other single-GPU configurations, each as a short run of this script in a child process (one after the other, before this
     process touches the device; nothing is exec'ed): C2 (Sponza-class, 262 k triangles, primary + shadow), C3 (C2 + 10 000 animated instances, the
     TLAS rebuilt every frame) and C4 as BASELINE.json words it (the 1 M-triangle scene path traced with NEE, max path length 3; 4 spp per call as
-    one of its modes).  Every child checks its own first and last timed frame against the oracle and times the oracle on its own workload."""
+    one of its modes).  Every child is a --full run: it checks its own first and last timed frame against the oracle and times the oracle on its
+    own workload."""
     import subprocess
     rows = {}
     todo = (("BASELINE config 2 (Sponza-class 262 k triangles, primary+shadow, static BVH)", ["--workload", "atrium262k"], False),
@@ -844,7 +861,7 @@ def baseline_configs(args):
     if not QUEUES_SET_BY_CALLER:
         env.pop("GPU_MAX_HW_QUEUES", None)  # (only a value the caller chose is passed on)
     for name, extra, with_modes in todo:
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.baseline_steps), "--warmup", "20", "--no-baseline-configs",
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.baseline_steps), "--warmup", "20", "--full", "--no-baseline-configs",
                "--cpu-seconds", "3", "--mode-frames", "32"] + extra + ([] if with_modes else ["--no-modes"]) + (["--procedural"] if args.procedural else [])
         t0 = time.time()
         try:

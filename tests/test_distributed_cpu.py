@@ -123,8 +123,8 @@ def test_bench_launcher_fails_when_a_rank_fails():
 
 
 def test_baseline_config_children_are_short_runs_of_the_same_script(monkeypatch):
-    """bench.py's headline run reports BASELINE.json's other single-GPU configurations (C2, C3, path-traced C4) as rows of config.modes, each
-    from a child run of the same script started BEFORE the parent touches the GPU.  No GPU here: the children are replaced by a fake that
+    """bench.py's --full headline run reports BASELINE.json's other single-GPU configurations (C2, C3, path-traced C4) as rows of config.modes,
+    each from a --full child run of the same script started BEFORE the parent touches the GPU.  No GPU here: the children are replaced by a fake that
     records their command lines and environments and answers with a bench line."""
     import importlib.util, json, subprocess, sys, types
     spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
@@ -151,7 +151,7 @@ def test_baseline_config_children_are_short_runs_of_the_same_script(monkeypatch)
     assert any("--workload atrium262k" in k for k in kinds) and any("--workload spheres10k" in k for k in kinds)
     assert any("--workload atrium1m --max-path-length 3" in k for k in kinds)
     for cmd, env in seen:
-        assert "--no-baseline-configs" in cmd and "--gpus" in cmd and cmd[cmd.index("--steps") + 1] == "200"
+        assert "--no-baseline-configs" in cmd and "--full" in cmd and "--gpus" in cmd and cmd[cmd.index("--steps") + 1] == "200"
         assert "GPU_MAX_HW_QUEUES" not in env and "WORLD_SIZE" not in env   # ... is not passed on to a child
     path_traced = [r for k, r in rows.items() if "config 4" in k][0]
     assert path_traced["modes"] == {"x": 1.0}                             # the child's own secondary modes ride along, its value row does not

@@ -301,7 +301,8 @@ def test_full_size_properties():
 @pytest.mark.parametrize("gather_format", ["f32", "f16", "bgra8"])
 def test_bench_two_ranks_on_one_gpu_gloo_hook(gather_format):
     """bench.py's N > 1 code path (tile shard, all-gather, assemble, max-over-ranks timing) with two processes sharing this GPU
-    through the gloo test hook (RCCL itself refuses two ranks on one device), for every format the tiles can travel in."""
+    through the gloo test hook (RCCL itself refuses two ranks on one device), for every format the tiles can travel in.  --full: the
+    batched mode and the check against the single-GPU frame."""
     import json
     import os
     import subprocess
@@ -310,7 +311,7 @@ def test_bench_two_ranks_on_one_gpu_gloo_hook(gather_format):
     env = dict(os.environ, RFW_BENCH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29577", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--workload", "cornell", "--width", "320", "--height", "200", "--no-cpu-baseline", "--gather-format", gather_format]
+           "--workload", "cornell", "--width", "320", "--height", "200", "--no-cpu-baseline", "--gather-format", gather_format, "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -338,7 +339,7 @@ def test_plain_bench_command_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RFW_BENCH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "cornell", "--width", "320", "--height", "200",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -371,13 +372,49 @@ def test_bench_two_ranks_on_one_gpu_p2p(present_rank):
     env = dict(os.environ, RFW_BENCH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29579", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "4",
-           "--workload", "cornell", "--width", "320", "--height", "200", "--no-cpu-baseline", "--collective", "p2p", "--present-rank", str(present_rank)]
+           "--workload", "cornell", "--width", "320", "--height", "200", "--no-cpu-baseline", "--collective", "p2p", "--present-rank", str(present_rank), "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["value"] > 0
     assert out["config"]["collective"] == "p2p" and out["config"]["sharded_frame_equals_single_gpu_frame"] is True
     assert "frame slots" in out["config"]["frames_in_flight_held_by"]
+
+
+def test_plain_bench_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """A plain bench.py run measures its `value` and nothing else; --full adds the secondary modes, the warm rebuild, the roofline and
+    the oracle leg around the same timed steps.  Both runs count the same rays and dump the same last frame, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--workload", "cornell", "--width", "320",
+           "--height", "200", "--mode-frames", "16", "--cpu-seconds", "0.5"]
+    lines = {}
+    for kind, extra in (("plain", []), ("full", ["--full"])):
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / kind)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[kind] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["metric"] == "Mrays/s (primary+shadow, 1spp)" and d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 6 and d["warmup"] == 2
+    assert plain["config"]["full"] is False and full["config"]["full"] is True
+    assert plain["config"]["rays_per_frame"] == full["config"]["rays_per_frame"] and plain["config"]["rays_timed"] == full["config"]["rays_timed"]
+    # plain: the value row and nothing measured besides it
+    assert [v.get("is_value") for v in plain["config"]["modes"].values()] == [True]
+    assert plain["roofline"] is None and "cpu_baseline" not in plain and "timed_frame_equals_oracle" not in plain["config"]
+    assert plain["config"]["bvh"]["build"] is None
+    # --full: the same line with everything else
+    assert sum(1 for v in full["config"]["modes"].values() if not v.get("is_value") and v["Mrays_per_s"] > 0) == 3, full["config"]["modes"]
+    assert full["roofline"]["contract"]["per_kernel"] and full["config"]["bvh"]["build"]["synchronize_warm_ms"]
+    assert full["cpu_baseline"]["value"] > 0
+    oracle_check = full["config"]["timed_frame_equals_oracle"]
+    assert oracle_check["first"]["rel_l2"] <= TOL and oracle_check["last"]["rel_l2"] <= TOL, oracle_check
+    assert plain["dump_outputs"] == full["dump_outputs"]
+    for name in plain["dump_outputs"]:
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8)), name
 
 
 def test_scale_script_dry_run_covers_every_exchange_and_format():

@@ -7,7 +7,7 @@
 cd "${GRAFT_REPO_ROOT:-$PWD}"
 for rep in 1 2 3; do for lib in $LIBS; do
   export RFW_HIP_LIB=$PWD/rfw-rs_amd/csrc/$lib
-  timeout 300 python3 bench.py --steps 400 --warmup 40 --no-cpu-baseline --procedural $BENCH_ARGS 2>/dev/null | tail -1 | python3 -c "
+  timeout 300 python3 bench.py --steps 400 --warmup 40 --full --no-cpu-baseline --procedural $BENCH_ARGS 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['roofline'].get('contract',{}).get('per_kernel',{})
 print('$lib', d['value'], d['ms_per_step'], {k: v['Mrays_per_s'] for k, v in d['config']['modes'].items() if not v.get('is_value')}, {k: v['ms'] for k, v in c.items()}, d['roofline'].get('lane_utilisation',{}).get('shadow'))"

@@ -9,7 +9,7 @@ for rep in $(seq 1 ${REPS:-3}); do for cfg in $CONFIGS; do
   (
     export RFW_HIP_LIB=$PWD/rfw-rs_amd/csrc/$lib
     for kv in ${envs//,/ }; do export "$kv"; done
-    timeout 300 python3 bench.py --steps ${STEPS:-400} --warmup 40 --no-cpu-baseline --procedural $BENCH_ARGS 2>/dev/null | tail -1 | python3 -c "
+    timeout 300 python3 bench.py --steps ${STEPS:-400} --warmup 40 --full --no-cpu-baseline --procedural $BENCH_ARGS 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['roofline'].get('contract',{}).get('per_kernel',{})
 print('$name', d['value'], d['ms_per_step'], {k: v['Mrays_per_s'] for k, v in d['config']['modes'].items() if not v.get('is_value')}, {k: v['ms'] for k, v in c.items()}, d['roofline'].get('lane_utilisation',{}), d['config'].get('timed_frame_equals_oracle'))"

@@ -2,6 +2,7 @@
 # A/B of any bench.py command line per configuration of environment overrides (one line per run: value, ms per frame, per-frame synchronize):
 #   gpurun -- 'CONFIGS="name:ENV=value,ENV=value name2:X=0" [REPS=2] BENCH_ARGS="--workload spheres10k --steps 200 --warmup 30" bash tools/ab_bench.sh tag'
 TAG=${1:-abb}
+BENCH_ARGS="--full $BENCH_ARGS"   # the per-frame synchronize and render-call times printed below are a --full run's
 cd "${GRAFT_REPO_ROOT:-$PWD}"
 mkdir -p gpurun_out/$TAG
 for rep in $(seq 1 ${REPS:-2}); do for cfg in $CONFIGS; do

@@ -2,6 +2,7 @@
 # Like tools/ab2.sh, but keeps the whole bench line per configuration and prints the traversal counters next to the rates:
 #   gpurun -- 'CONFIGS="name:library:ENV=value,..." [BENCH_ARGS=...] bash tools/ab_json.sh tag'
 TAG=${1:-abj}
+BENCH_ARGS="--full $BENCH_ARGS"   # the modes, per-kernel times and build timings printed below are a --full run's
 cd "${GRAFT_REPO_ROOT:-$PWD}"
 mkdir -p gpurun_out/$TAG
 for rep in $(seq 1 ${REPS:-1}); do for cfg in $CONFIGS; do

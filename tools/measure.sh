@@ -26,10 +26,10 @@ profile_config() { # name, bench arguments...
   local O=$OUT/$cfg
   mkdir -p $O
   cd $R
-  python3 bench.py "$@" > $O/bench.json 2> $O/bench.err
+  python3 bench.py --full "$@" > $O/bench.json 2> $O/bench.err
   # profiler passes: the program itself after `--`, kernel trace and counters in separate runs, shortened, without the oracle leg and the extra modes
   cd /tmp; export TMPDIR=/tmp
-  local B="python3 $R/bench.py --steps 48 --warmup 8 --no-cpu-baseline --no-modes $*"
+  local B="python3 $R/bench.py --steps 48 --warmup 8 --full --no-cpu-baseline --no-modes $*"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $B > $O/bench_under_rocprof.json 2> $O/trace.err
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_one -- $B --frames-in-flight 1 > $O/bench_one_at_a_time.json 2> $O/trace_one.err
   pmc() { # name, counters...
@@ -70,21 +70,21 @@ if [ -z "$QUICK" ]; then
   # far outside every cache: the same atrium at 33.5 M triangles (the one configuration where the "% of HBM roofline" clause has a meaning)
   if [ -n "$WITH_32M" ]; then profile_config c32m --workload atrium32m --procedural --no-cpu-baseline; fi
   cd $R
-  python3 bench.py --identical-frames --no-cpu-baseline > $OUT/bench_atrium1m_identical_frames.json 2> $OUT/bench_identical.err
+  python3 bench.py --full --identical-frames --no-cpu-baseline > $OUT/bench_atrium1m_identical_frames.json 2> $OUT/bench_identical.err
   [ -s $OUT/bench_atrium1m_identical_frames.json ] && cp $OUT/bench_atrium1m_identical_frames.json profiles/${TAG}_c4_bench_identical_frames.json
 fi
 cd $R
 rocprofv3 -L > $OUT/counters_available.txt 2>&1
 # the counters are in: the bench lines of the round, now WITH the ceilings of their configuration (bench.py reads profiles/<tag>_<cfg>_pmc*.json)
-python3 bench.py > $OUT/bench_c4_final.json 2> $OUT/bench_c4_final.err && cp $OUT/bench_c4_final.json profiles/${TAG}_c4_bench.json
+python3 bench.py --full > $OUT/bench_c4_final.json 2> $OUT/bench_c4_final.err && cp $OUT/bench_c4_final.json profiles/${TAG}_c4_bench.json
 if [ -z "$QUICK" ]; then
-  python3 bench.py --workload atrium262k > $OUT/bench_c2_final.json 2>> $OUT/bench_c4_final.err && cp $OUT/bench_c2_final.json profiles/${TAG}_c2_bench.json
-  python3 bench.py --workload spheres10k > $OUT/bench_c3_final.json 2>> $OUT/bench_c4_final.err && cp $OUT/bench_c3_final.json profiles/${TAG}_c3_bench.json
-  python3 bench.py --max-path-length 3 > $OUT/bench_c4path_final.json 2>> $OUT/bench_c4_final.err && cp $OUT/bench_c4path_final.json profiles/${TAG}_c4path_bench.json
-  if [ -n "$WITH_32M" ]; then python3 bench.py --workload atrium32m --procedural --no-cpu-baseline > $OUT/bench_c32m_final.json 2>> $OUT/bench_c4_final.err && cp $OUT/bench_c32m_final.json profiles/${TAG}_c32m_bench.json; fi
+  python3 bench.py --full --workload atrium262k > $OUT/bench_c2_final.json 2>> $OUT/bench_c4_final.err && cp $OUT/bench_c2_final.json profiles/${TAG}_c2_bench.json
+  python3 bench.py --full --workload spheres10k > $OUT/bench_c3_final.json 2>> $OUT/bench_c4_final.err && cp $OUT/bench_c3_final.json profiles/${TAG}_c3_bench.json
+  python3 bench.py --full --max-path-length 3 > $OUT/bench_c4path_final.json 2>> $OUT/bench_c4_final.err && cp $OUT/bench_c4path_final.json profiles/${TAG}_c4path_bench.json
+  if [ -n "$WITH_32M" ]; then python3 bench.py --full --workload atrium32m --procedural --no-cpu-baseline > $OUT/bench_c32m_final.json 2>> $OUT/bench_c4_final.err && cp $OUT/bench_c32m_final.json profiles/${TAG}_c32m_bench.json; fi
 fi
-# the driver's own command (one fill-and-drain of the frame slots) and the builder's timings, for BASELINE.md / DESIGN.md
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_c4_20_steps.json 2> $OUT/bench_c4_20_steps.err && cp $OUT/bench_c4_20_steps.json profiles/${TAG}_c4_bench_20_steps.json
+# the driver's own command, --full (one fill-and-drain of the frame slots) and the builder's timings, for BASELINE.md / DESIGN.md
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_c4_20_steps.json 2> $OUT/bench_c4_20_steps.err && cp $OUT/bench_c4_20_steps.json profiles/${TAG}_c4_bench_20_steps.json
 if [ -z "$QUICK" ]; then
   python3 tools/probes/build_time.py 0 > $OUT/build_time.json 2> $OUT/build_time.err && cp $OUT/build_time.json profiles/${TAG}_build_time.json
 fi

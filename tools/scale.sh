@@ -4,7 +4,7 @@
 # Runs the plain command `python3 bench.py --gpus N` (bench.py starts its N ranks itself, one per GPU, when no launcher has: launch_ranks;
 # under `python -m torch.distributed.run` the same script is one of the launcher's ranks) for every N in $GPUS and, at N > 1, for every
 # (collective, gather format) pair in $VARIANTS; prints one row per run with the whole-job rate, the speed-up over N = 1, and whether the
-# sharded frame equalled the single-GPU frame (config.sharded_frame_equals_single_gpu_frame: rank 0 re-renders the last timed frames on one
+# sharded frame equalled the single-GPU frame (config.sharded_frame_equals_single_gpu_frame of a --full run: rank 0 re-renders the last timed frames on one
 # GPU and compares in the format that travelled).  Raw lines: gpurun_out/<tag>/scale_*.json; table: gpurun_out/<tag>/scale.md.
 # On a 1-GPU box only the N = 1 row runs (RCCL refuses two ranks on one device); RFW_BENCH_DIST_BACKEND=gloo lets 2 ranks share a GPU for a
 # functional check of the other rows (tests/test_gpu_parity.py does that).
@@ -24,7 +24,7 @@ if [ "$1" = "--dry" ]; then
     barg=""; case "$v" in *batched) barg="--batch 8";; esac   # (default: one exchange per FRAME, north_star's protocol; batched: one per 8 frames)
     PORT=$((PORT + 1)); f=$OUT/dry_${v//:/_}.json
     env $extra timeout 600 python3 bench.py --gpus 2 \
-      --steps 12 --warmup 4 --workload cornell --width 320 --height 200 --no-cpu-baseline --collective "$coll" --gather-format "$fmt" $barg > "$f" 2> "${f%.json}.err"
+      --steps 12 --warmup 4 --workload cornell --width 320 --height 200 --no-cpu-baseline --full --collective "$coll" --gather-format "$fmt" $barg > "$f" 2> "${f%.json}.err"
     rc=$?
     ok=$(python3 -c "import json,sys; l=[x for x in open('$f') if x.startswith('{')]; d=json.loads(l[-1]) if l else {}; print(int(d.get('config',{}).get('sharded_frame_equals_single_gpu_frame') is True and d.get('n_gpus')==2 and d.get('config',{}).get('ranks_seen')==2))" 2>/dev/null)
     if [ "$rc" -ne 0 ] || [ "$ok" != "1" ]; then FAILED="$FAILED $v(rc=$rc)"; echo "FAIL $v"; tail -5 "${f%.json}.err"; else echo "ok   $v"; fi
@@ -56,7 +56,7 @@ run() { # n collective format [batched]
     python3 bench.py --gpus 1 --steps "$STEPS" --warmup 24 --no-cpu-baseline --no-modes > "$f" 2> "${f%.json}.err"
   else
     python3 bench.py --gpus "$n" \
-      --steps "$STEPS" --warmup 24 --no-cpu-baseline --collective "$coll" --gather-format "$fmt" $extra > "$f" 2> "${f%.json}.err"
+      --steps "$STEPS" --warmup 24 --no-cpu-baseline --full --collective "$coll" --gather-format "$fmt" $extra > "$f" 2> "${f%.json}.err"
   fi
   echo "$n $coll ${fmt}${lat:+(one-exchange-per-8-frames)} $f" >> "$ROWS"
 }
