@@ -198,7 +198,15 @@ RFW_HIP_API int rfw_hip_synchronize(void* instance);
  *   FILTERED_SSAO  the accumulator of SSAO; the frame is an edge-aware filter of acc.x / n guided by the primary hit's normal and
  *                  distance (DESIGN.md "Render modes").  With world > 1 the guides stay on their ranks: the frame finalises as SSAO.
  * A change of mode starts a new image (as a change of view); render_batch / render_samples always render DEFAULT.  Options "ao_samples"
- * (1-8, default 4) and "ao_radius" (world units; 0 = 5 % of the diagonal of the scene's bounds, the default) restart accumulation. */
+ * (1-8, default 4) and "ao_radius" (world units; 0 = 5 % of the diagonal of the scene's bounds, the default) restart accumulation.
+ * Option "denoise" = k (0 = off, the default; 1-5): DEFAULT frames (rfw_hip_render mode 0 / unknown, rfw_hip_render_samples; every frame slot,
+ * with sub-streams) are finalised by k passes (steps 1, 2, 4, 8, 16 pixels) of an edge-avoiding a-trous filter of the albedo-demodulated
+ * radiance, guided by the latest sample's primary hit (DESIGN.md "Denoiser"); "denoise_colour" is its colour edge-stopping width (> 0, in
+ * units of demodulated radiance).  Only the finalised frame changes (read_framebuffer*, download_frame what = 0 and 2): the accumulator
+ * (read_accumulator*, download_frame what = 1) stays the raw sum.  Out of scope: rfw_hip_render_batch (its frames finalise unfiltered) and
+ * world > 1 or any exchange of tiles (the guides stay on their ranks: the frame finalises unfiltered, as FILTERED_SSAO finalises as SSAO
+ * there); modes 1-6 ignore the option.  Setting either option to a different value restarts accumulation.  The filter assumes a finite
+ * accumulator ("clamp_value"); a NaN or Inf pixel is skipped as a tap and spoils only itself. */
 enum {
     RFW_HIP_RENDER_DEFAULT = 0,
     RFW_HIP_RENDER_NORMAL = 1,
@@ -226,8 +234,11 @@ RFW_HIP_API int rfw_hip_set_skins(void* instance, const rfw_skin_data* skins, ui
 RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
 /* Options (unknown keys are an error).  The trait has none: these are the knobs a host outside the trait may turn.
  *   rendering      "max_path_length" (1 = primary + shadow), "clamp_value", "nee" (0 / 1), "sample_count", "sky_r" / "sky_g" / "sky_b",
- *                  "texture_array" (gpu-rt's 1024^2 x 5 texture array, default 1), "ao_samples" / "ao_radius" (render modes 5, 6)
- *   measurement    "count_traversal" (node / triangle / instance counters of the next frames), "timing" (HIP events per kernel)
+ *                  "texture_array" (gpu-rt's 1024^2 x 5 texture array, default 1), "ao_samples" / "ao_radius" (render modes 5, 6),
+ *                  "denoise" 0 (off, default) | 1 ... 5 a-trous passes over the path-traced frame, "denoise_colour" (> 0) — any other value
+ *                  of either is RFW_HIP_E_INVALID; see rfw_hip_render
+ *   measurement    "count_traversal" (node / triangle / instance counters of the next frames), "timing" (HIP events per kernel),
+ *                  "denoise_form" 0 | 1 | 2 (the a-trous kernel form: the faster one per step | direct | tiled; the image is the same)
  *   ray order      "shadow_order" 0 | 1 | 2 (which end any-hit traversals start from; the image is the same under every order),
  *                  "sort_extension_rays" 0 never | 1 always | 2 batches whose bounces do not stream (default),
  *                  "stream_run" r (0 or a power of two <= 64: a wavefront of the bounces' trace kernels owns r x 64 queue entries and refills
@@ -338,7 +349,9 @@ RFW_HIP_API int rfw_hip_occludes4(void* instance, const float* origin_xyz4, cons
                                   uint8_t* occluded4);
 
 /* Debug read-back of the wavefront queues after the last render() bounce `bounce`
- * (test-only; enabled by option "keep_queues"=1).  Layout documented in DESIGN.md. */
+ * (test-only; enabled by option "keep_queues"=1).  Layout documented in DESIGN.md.
+ * "dn_guide" (option "denoise"): the guide of the latest denoised frame, three float4 planes of width * height frame pixels, plane after
+ * plane: (faced geometric normal, t), (hit point, 0), (albedo, f) with f = 1 where the pixel is filtered, 0 where it passes through. */
 RFW_HIP_API int rfw_hip_debug_read(void* instance, const char* what, void* dst, uint64_t bytes, uint64_t* written);
 
 /* occludes() that also reports how many 4-wide nodes each any-hit traversal visited (the any-hit counterpart of rfw_hip_depth_test).  For

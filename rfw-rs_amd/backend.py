@@ -502,3 +502,8 @@ class HipBackend:
         w = C.c_uint64(0)
         self._check(self._l.rfw_hip_debug_read(self._h, what.encode(), buf.ctypes.data, nbytes, C.byref(w)))
         return buf[: int(w.value)]
+
+    def denoise_guide(self):
+        """The denoiser's guide of the latest frame (option "denoise"): g0 = (faced gN, t), g1 = (P, 0), g2 = (albedo, f), each (H, W, 4)."""
+        g = np.frombuffer(self.debug_read("dn_guide", 48 * self.width * self.height).tobytes(), np.float32)
+        return tuple(g.reshape(3, self.height, self.width, 4))

@@ -34,6 +34,65 @@ RFW_DI f3 cosine_about(const f3 n, const float r0, const float r1)
     return normalize(t * l.x + bt * l.y + n * l.z);
 }
 
+// What the camera ray of a slab slot sees (S, O4, D4: k_primary's hit[0], ray_o[0], ray_d[0] of a slot whose ray HIT): k_shade at bounce 0,
+// step for step (kernels.hip) — the same normal, tangent frame and material colour.  Shared by k_aov and the denoiser's guide (denoise.inc).
+struct PrimarySurface {
+    f3 P, gN, N, albedo; // O + t D, the faced geometric normal, the faced (normal-mapped) shading normal, material colour x diffuse map
+    float t;
+    bool light; // an emitter as k_shade sees it: a colour component above 1 and no emissive map
+};
+RFW_DI PrimarySurface primary_surface(const CameraParams& cam, const SceneDev& sc, const uint4 S, const float4 O4, const float4 D4)
+{
+    PrimarySurface ps;
+    const f3 O = mk3(O4.x, O4.y, O4.z), D = mk3(D4.x, D4.y, D4.z);
+    const int32_t INST_ID = (int32_t)S.x;
+    const uint32_t TRI_ID = S.y;
+    const float t_hit = bitsf(S.z);
+    f3 P, gN;
+    const float4* tp = reinterpret_cast<const float4*>(sc.triangles + TRI_ID);
+    const float4 q3 = tp[3], q4 = tp[4], q5 = tp[5], q6 = tp[6], T0 = tp[7], T1 = tp[8], T2 = tp[9];
+    const uint4 q10 = *reinterpret_cast<const uint4*>(tp + 10);
+    ShadingData sd = extractParameters(sc.materials + (int32_t)q10.y);
+    const float u = (float)(S.w & 65535u) * (1.0f / 65535.0f);
+    const float v = (float)(S.w >> 16) * (1.0f / 65535.0f);
+    const float w = 1.0f - u - v;
+    gN = mk3(q3.x, q3.y, q3.z);
+    f3 N = w * mk3(q4.x, q4.y, q4.z) + u * mk3(q5.x, q5.y, q5.z) + v * mk3(q6.x, q6.y, q6.z);
+    f3 T = w * mk3(T0.x, T0.y, T0.z) + u * mk3(T1.x, T1.y, T1.z) + v * mk3(T2.x, T2.y, T2.z);
+    const float Tw = w * T0.w + u * T1.w + v * T2.w;
+    const float4* np = reinterpret_cast<const float4*>(sc.instance_normals + INST_ID);
+    const float4 n0 = np[0], n1 = np[1], n2 = np[2];
+    gN = normalize(xform_rows(n0, n1, n2, gN, 0.0f));
+    N = normalize(xform_rows(n0, n1, n2, N, 0.0f));
+    T = normalize(xform_rows(n0, n1, n2, T, 0.0f));
+    const f3 B = cross(N, T) * Tw;
+    P = O + t_hit * D;
+    const bool light = (sd.color.x > 1.0f || sd.color.y > 1.0f || sd.color.z > 1.0f) && !(sd.flags & RFW_MAT_HAS_EMISSIVE_MAP);
+    if ((sd.flags & 63u) != 0u) {
+        const float lambda = __builtin_sqrtf(bitsf(q10.z)) + rfw_log2f(cam.spread_angle * (1.0f / gl_abs(dot(D, N))));
+        const float4 q0 = tp[0], q1 = tp[1], q2 = tp[2];
+        const float tu = w * q0.w + u * q1.w + v * q2.w;
+        const float tv = w * q3.w + u * q4.w + v * q5.w;
+        if (!light && (sd.flags & RFW_MAT_HAS_DIFFUSE_MAP) && sd.diffuse_map >= 0 && (uint32_t)sd.diffuse_map < sc.n_textures) {
+            const f4 c = fetchTexelTrilinear(sc.tex_data, sc.tex_desc[sd.diffuse_map], lambda, tu, tv);
+            sd.color = sd.color * mk3(c.x, c.y, c.z);
+        }
+        if (!light && (sd.flags & RFW_MAT_HAS_NORMAL_MAP) && sd.normal_map >= 0 && (uint32_t)sd.normal_map < sc.n_textures) {
+            const f4 c = texture_sample(sc.tex_data, sc.tex_desc[sd.normal_map], tu, tv, (float)f2i(lambda));
+            const f3 m = (mk3(c.x, c.y, c.z) - mk3(0.5f)) * 2.0f;
+            N = normalize((T * m.x + B * m.y) + N * m.z);
+        }
+    }
+    if (dot(D, gN) >= 0.0f) { // back facing
+        N = N * -1.0f;
+        gN = gN * -1.0f;
+    }
+    ps.P = P; ps.gN = gN; ps.N = N; ps.albedo = sd.color;
+    ps.t = t_hit;
+    ps.light = light;
+    return ps;
+}
+
 __global__ __launch_bounds__(256) void k_aov(const CameraParams cam, const SceneDev sc, const PathDev p, const AovParams ap)
 {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
@@ -49,51 +108,13 @@ __global__ __launch_bounds__(256) void k_aov(const CameraParams cam, const Scene
     f3 P = mk3(0.0f), gN = mk3(0.0f);
     float t_hit = 0.0f;
     if (hit) {
-        const f3 O = mk3(O4.x, O4.y, O4.z), D = mk3(D4.x, D4.y, D4.z);
-        const int32_t INST_ID = (int32_t)S.x;
-        const uint32_t TRI_ID = S.y;
-        t_hit = bitsf(S.z);
-        // k_shade at bounce 0, step for step (kernels.hip): the same normal, tangent frame and material colour
-        const float4* tp = reinterpret_cast<const float4*>(sc.triangles + TRI_ID);
-        const float4 q3 = tp[3], q4 = tp[4], q5 = tp[5], q6 = tp[6], T0 = tp[7], T1 = tp[8], T2 = tp[9];
-        const uint4 q10 = *reinterpret_cast<const uint4*>(tp + 10);
-        ShadingData sd = extractParameters(sc.materials + (int32_t)q10.y);
-        const float u = (float)(S.w & 65535u) * (1.0f / 65535.0f);
-        const float v = (float)(S.w >> 16) * (1.0f / 65535.0f);
-        const float w = 1.0f - u - v;
-        gN = mk3(q3.x, q3.y, q3.z);
-        f3 N = w * mk3(q4.x, q4.y, q4.z) + u * mk3(q5.x, q5.y, q5.z) + v * mk3(q6.x, q6.y, q6.z);
-        f3 T = w * mk3(T0.x, T0.y, T0.z) + u * mk3(T1.x, T1.y, T1.z) + v * mk3(T2.x, T2.y, T2.z);
-        const float Tw = w * T0.w + u * T1.w + v * T2.w;
-        const float4* np = reinterpret_cast<const float4*>(sc.instance_normals + INST_ID);
-        const float4 n0 = np[0], n1 = np[1], n2 = np[2];
-        gN = normalize(xform_rows(n0, n1, n2, gN, 0.0f));
-        N = normalize(xform_rows(n0, n1, n2, N, 0.0f));
-        T = normalize(xform_rows(n0, n1, n2, T, 0.0f));
-        const f3 B = cross(N, T) * Tw;
-        P = O + t_hit * D;
-        const bool light = (sd.color.x > 1.0f || sd.color.y > 1.0f || sd.color.z > 1.0f) && !(sd.flags & RFW_MAT_HAS_EMISSIVE_MAP);
-        if ((sd.flags & 63u) != 0u) {
-            const float lambda = __builtin_sqrtf(bitsf(q10.z)) + rfw_log2f(cam.spread_angle * (1.0f / gl_abs(dot(D, N))));
-            const float4 q0 = tp[0], q1 = tp[1], q2 = tp[2];
-            const float tu = w * q0.w + u * q1.w + v * q2.w;
-            const float tv = w * q3.w + u * q4.w + v * q5.w;
-            if (!light && (sd.flags & RFW_MAT_HAS_DIFFUSE_MAP) && sd.diffuse_map >= 0 && (uint32_t)sd.diffuse_map < sc.n_textures) {
-                const f4 c = fetchTexelTrilinear(sc.tex_data, sc.tex_desc[sd.diffuse_map], lambda, tu, tv);
-                sd.color = sd.color * mk3(c.x, c.y, c.z);
-            }
-            if (!light && (sd.flags & RFW_MAT_HAS_NORMAL_MAP) && sd.normal_map >= 0 && (uint32_t)sd.normal_map < sc.n_textures) {
-                const f4 c = texture_sample(sc.tex_data, sc.tex_desc[sd.normal_map], tu, tv, (float)f2i(lambda));
-                const f3 m = (mk3(c.x, c.y, c.z) - mk3(0.5f)) * 2.0f;
-                N = normalize((T * m.x + B * m.y) + N * m.z);
-            }
-        }
-        if (dot(D, gN) >= 0.0f) { // back facing
-            N = N * -1.0f;
-            gN = gN * -1.0f;
-        }
+        const PrimarySurface ps = primary_surface(cam, sc, S, O4, D4);
+        const f3 N = ps.N;
+        P = ps.P;
+        gN = ps.gN;
+        t_hit = ps.t;
         if (ap.mode == RFW_HIP_RENDER_NORMAL) value = make_float4(N.x, N.y, N.z, 0.0f);
-        else if (ap.mode == RFW_HIP_RENDER_ALBEDO) value = make_float4(sd.color.x, sd.color.y, sd.color.z, 0.0f);
+        else if (ap.mode == RFW_HIP_RENDER_ALBEDO) value = make_float4(ps.albedo.x, ps.albedo.y, ps.albedo.z, 0.0f);
         else if (ap.mode == RFW_HIP_RENDER_GBUFFER) value = make_float4(P.x, P.y, P.z, t_hit);
         else if (ap.mode == RFW_HIP_RENDER_SCREEN_SPACE) {
             const f3 pos = mk3(cam.pos[0], cam.pos[1], cam.pos[2]), rel = P - pos;

@@ -267,6 +267,15 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
     const bool ao = mode >= RFW_HIP_RENDER_SSAO;
     const uint32_t ao_rounds = ao ? I->ao_samples : 0u;
     if (ao) HIP_TRY(I, I->d_ao_guide.ensure((size_t)I->width * I->height));
+    // option "denoise": the a-trous filter finalises the path-traced frame where launch_assemble would (the frame is de-tiled on this device
+    // and the call leaves ONE image behind); everywhere else the option changes nothing
+    const bool dn = I->denoise > 0 && mode == RFW_HIP_RENDER_DEFAULT && (k == 1 || samples) && I->world <= 1 && !scene_of(I)->comm && !scene_of(I)->loop &&
+                    !scene_of(I)->p2p.connected;
+    if (dn) {
+        const size_t px = (size_t)I->width * I->height;
+        HIP_TRY(I, I->d_dn_guide.ensure(3 * px));
+        for (int q = 0; q < 2 && I->denoise > 1; q++) HIP_TRY(I, I->d_dn_plane[q].ensure(px));
+    }
 
     if (tm) (void)hipEventRecord(I->events[EV_FRAME0], main);
     // queue counters: this frame takes the block the previous frame's k_primary cleared (alloc_paths cleared both), and clears the other
@@ -356,6 +365,15 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
                 launch_extend(st[s], cam[s], sc[s], p[s], b, count, order);
             }
             if (tm) (void)hipEventRecord(ev[ev_index(b, 0, 1)], st[s]);
+            if (b == 0 && dn) { // the filter's guide, before k_shade and bounce 2 reuse the [0] buffers; of k samples, the LAST one's
+                PathDev g = p[s];
+                if (k > 1) {
+                    const size_t last = (size_t)(k - 1u) * I->cap_v;
+                    g.hit[0] += last; g.ray_o[0] += last; g.ray_d[0] += last;
+                    g.capacity = I->cap_v;
+                }
+                launch_dn_guide(st[s], cam[s], sc[s], g, I->d_dn_guide.ptr, k > 1 ? 0x00ffffffu : 0xffffffffu);
+            }
         }
         for (uint32_t s = 0; s < S; s++) {
             hipEvent_t* ev = ring_events(I, slot, s);
@@ -403,7 +421,12 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         if (prc != RFW_HIP_OK) return prc;
     } else if (I->world <= 1) // de-tile the sub-slabs into the linear accumulator / tonemapped frame (blit.comp:15-23)
     {
-        if (mode == RFW_HIP_RENDER_FILTERED_SSAO) launch_ao_filter(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_ao_guide.ptr, I->d_frame_out.ptr, I->sample_count);
+        if (dn) {
+            float4* const planes[2] = {I->d_dn_plane[0].ptr, I->d_dn_plane[1].ptr};
+            launch_atrous(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_dn_guide.ptr, planes, I->d_frame_out.ptr, I->sample_count, I->denoise, I->denoise_colour,
+                          I->denoise_form);
+        }
+        else if (mode == RFW_HIP_RENDER_FILTERED_SSAO) launch_ao_filter(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_ao_guide.ptr, I->d_frame_out.ptr, I->sample_count);
         else launch_assemble(main, cam[0], I->d_acc_slab.ptr, false, false, I->cap_v, I->d_frame_out.ptr, I->sample_count, mode != RFW_HIP_RENDER_DEFAULT);
         I->acc_source = I->d_acc_slab.ptr; I->acc_source_rgb = false; I->acc_source_batch = frames_out;
     }
@@ -611,6 +634,7 @@ void rfw_hip_destroy(void* inst)
         }
         for (int h = 0; h < 2; h++) { I->d_ray_o[h].release(); I->d_ray_d[h].release(); I->d_thr[h].release(); I->d_hit[h].release(); }
         I->d_sh_o.release(); I->d_sh_d.release(); I->d_sh_e.release(); I->d_acc_slab.release(); I->d_frame_acc.release(); I->d_frame_out.release(); I->d_present.release();
+        I->d_dn_guide.release(); I->d_dn_plane[0].release(); I->d_dn_plane[1].release();
         for (auto& ev : I->ring)
             if (ev) (void)hipEventDestroy(ev);
         if (I->ev_fork) (void)hipEventDestroy(I->ev_fork);
@@ -649,6 +673,7 @@ static int render_impl(Instance* I, const rfw_camera_view_3d* views, uint32_t k,
         cur->max_path_length = I->max_path_length; cur->clamp_value = I->clamp_value; cur->flags = I->flags; cur->timing = I->timing;
         for (int c = 0; c < 3; c++) cur->sky[c] = I->sky[c];
         cur->ao_samples = I->ao_samples; cur->ao_radius = I->ao_radius;
+        cur->denoise = I->denoise; cur->denoise_colour = I->denoise_colour; cur->denoise_form = I->denoise_form;
     }
     int rc = ensure_slot_tlas(I, cur);
     if (rc == RFW_HIP_OK) rc = do_render(cur, views, k, samples, mode);
@@ -770,6 +795,23 @@ int rfw_hip_set_option(void* inst, const char* key, double value)
         }
         I->sample_count = 0;
         I->restart = true;
+    }
+    else if (k == "denoise" || k == "denoise_colour") { // the filter of the path-traced frame (denoise.inc): a changed value starts a new image
+        if (k == "denoise") {
+            if (!(value >= 0.0 && value <= (double)kDenoiseMaxPasses) || value != std::floor(value)) return fail(I, RFW_HIP_E_INVALID, "set_option: denoise is 0 (off) or 1 ... 5 passes");
+            if ((uint32_t)value == I->denoise) return RFW_HIP_OK;
+            I->denoise = (uint32_t)value;
+        } else {
+            if (!(value > 0.0) || !std::isfinite(value) || !((float)value > 0.0f) || !std::isfinite((float)value)) return fail(I, RFW_HIP_E_INVALID, "set_option: denoise_colour is > 0");
+            if ((float)value == I->denoise_colour) return RFW_HIP_OK;
+            I->denoise_colour = (float)value;
+        }
+        I->sample_count = 0;
+        I->restart = true;
+    }
+    else if (k == "denoise_form") { // measurement: which kernel form the passes take (0 = the faster one per step, 1 direct, 2 tiled); the image is the same
+        if (value != 0.0 && value != 1.0 && value != 2.0) return fail(I, RFW_HIP_E_INVALID, "set_option: denoise_form is 0, 1 or 2");
+        I->denoise_form = (uint32_t)value;
     }
     else if (k == "gather_format") { // 0 f32 accumulator RGB, 1 f16 finished frame, 2 presented BGRA8 (sharded frames only)
         if (value < 0 || value > 2) return fail(I, RFW_HIP_E_INVALID, "set_option: gather_format is 0, 1 or 2");

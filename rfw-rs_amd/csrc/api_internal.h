@@ -477,6 +477,13 @@ struct Instance {
     uint64_t ao_auto_version = 0;
     uint32_t ao_rounds = 0;            // per slot: AO rounds of the latest frame (0: it traced none, "ao_rays" is empty)
     DevBuf<float4> d_ao_guide;         // per slot: width x height (faced gN, t), written by k_aov in modes 5 and 6
+    // option "denoise" (denoise.inc): a-trous passes over the finalised path-traced frame (0 = off), the colour width sigma_c, the kernel form
+    // (0 = as measured per step, 1 direct, 2 tiled); per slot: the guide of the latest frame (three planes) and the two ping-pong colour planes,
+    // allocated at the first denoised frame
+    uint32_t denoise = 0;
+    float denoise_colour = kDenoiseDefaultColour;
+    uint32_t denoise_form = 0;
+    DevBuf<float4> d_dn_guide, d_dn_plane[2];
     std::vector<hipEvent_t> ring;  // [kTimingRing][substreams][kNumEvents]
     hipEvent_t* events = nullptr;   // event set of the current frame, sub-shard 0
     uint32_t substreams = 1;        // the frame's tiles are dealt to this many sub-shards, each traced on its own stream

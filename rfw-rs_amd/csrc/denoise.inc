@@ -1,0 +1,216 @@
+// denoise.inc — option "denoise" (include/rfw_hip.h, DESIGN.md "Denoiser"): an edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) of
+// the albedo-demodulated radiance of the path-traced frame, guided by the primary hit, in place of k_assemble.  Included by kernels.hip inside
+// namespace rfwhip, after aov.inc (primary_surface) and finalise<>.
+//
+//   k_dn_guide  after k_primary at bounce 0, before k_shade: per frame pixel three float4 planes, g0 = (faced gN, t), g1 = (P, 0),
+//               g2 = (albedo, f); f = 1 where the pixel is filtered (the camera ray hit something that is not a light), else 0
+//   k_atrous    pass i of k, step s = 2^i: x_{i+1}(p) = sum_q w(p, q) x_i(q) / sum_q w(p, q) over the 5 x 5 taps q = p + s (dx, dy) inside the
+//               frame with f(q) = 1.  The first pass reads the accumulator slab and demodulates (x_0 = (acc / n) / max(albedo, kDnAlbedoFloor)),
+//               the last one remodulates, takes k_assemble's square root and writes the frame; pixels with f = 0 pass through with k_assemble's
+//               finalise.  Between passes x travels in float4 planes whose w holds f.
+//
+// Two forms of a pass.  DIRECT: one thread per pixel, 25 taps straight from memory.  TILED: for step s the pixels with equal (x mod s, y mod s)
+// form s^2 sub-images on each of which the pass is a dense 5 x 5 filter; a workgroup takes 16 x 16 pixels of ONE sub-image and stages their
+// 20 x 20 window of (x, g0, g1) in LDS once.  LDS rows are kDnPitch = 32 float4 apart: a ds_read_b128 is served in groups of 16 lanes that span
+// two rows of the tile (lanes 0-3, 12-15 of one row with lanes 4-11 of the next), and those hit 16 different 16-byte slots of the 256-byte bank
+// row only when the pitch is a multiple of 16 slots.
+
+constexpr float kDnPlane = 0.02f;       // wp = max(0, 1 - |dot(gN_p, P_q - P_p)| / (kDnPlane t_p)): distance from p's tangent plane, relative to the viewing distance
+constexpr int kDnNormalSquarings = 5;   // wn = max(0, dot(gN_p, gN_q))^32
+constexpr float kDnAlbedoFloor = 1e-3f; // demodulation divides by max(albedo, this) per channel
+constexpr int kDnTile = 16, kDnRadius = 2, kDnSpan = kDnTile + 2 * kDnRadius, kDnPitch = 32;
+constexpr float kDnH[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+// which form pass i (step 2^i) takes unless option "denoise_form" forces one.  Timed per step at 1080p on the MI355X (EXPERIMENTS.md, "denoiser"):
+// tiled 0.16 / 0.10 / 0.13 / 0.21 / 0.16 ms for steps 1 .. 16 against direct 0.57 / 0.22 / 0.17 / 0.20 / 0.30 — tiled everywhere (step 8 is a tie)
+constexpr bool atrous_tiled_by_default(uint32_t /*pass*/) { return true; }
+
+struct DnParams {
+    const float4* acc;    // the instance's accumulator slab(s), as k_assemble reads them
+    uint64_t slab_elems;
+    const float4* guide;  // g0, g1, g2: three planes of width x height
+    const float4* in;     // x_i (rgb, f): passes after the first
+    float4* out;          // x_{i+1} (rgb, f), or the frame (last pass)
+    uint32_t samples;     // n, the sample just traced included
+    uint32_t step_shift;  // s = 1 << step_shift
+    float inv_sigma2;     // 1 / sigma_i^2, sigma_i = sigma_c 2^-i / sqrt(n)
+};
+
+__global__ __launch_bounds__(256) void k_dn_guide(const CameraParams cam, const SceneDev sc, const PathDev p, float4* __restrict__ guide, const uint32_t pixel_mask)
+{
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= p.capacity) return;
+    const uint4 S = p.hit[0][idx];
+    if (S.x == kNoPath) return; // a slab slot without a pixel
+    const float4 O4 = p.ray_o[0][idx], D4 = p.ray_d[0][idx];
+    const uint32_t px = fbits(O4.w) & pixel_mask; // (a batch of samples carries the sample's index above the pixel's)
+    const uint32_t plane = cam.width * cam.height;
+    if (px >= plane) return;
+    float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g1 = g0, g2 = g0;
+    if ((int32_t)S.x >= 0) {
+        const PrimarySurface ps = primary_surface(cam, sc, S, O4, D4);
+        g0 = make_float4(ps.gN.x, ps.gN.y, ps.gN.z, ps.t);
+        g1 = make_float4(ps.P.x, ps.P.y, ps.P.z, 0.0f);
+        g2 = make_float4(ps.albedo.x, ps.albedo.y, ps.albedo.z, ps.light ? 0.0f : 1.0f);
+    }
+    guide[px] = g0;
+    guide[(size_t)plane + px] = g1;
+    guide[2u * (size_t)plane + px] = g2;
+}
+
+struct DnPixel { float4 x, g0, g1; }; // x.w = f; g0, g1 are read only where f = 1
+
+template <bool FIRST> RFW_DI DnPixel dn_load(const CameraParams& cam, const DnParams& dp, const int x, const int y)
+{
+    DnPixel r;
+    r.x = r.g0 = r.g1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f); // outside the frame, or not filtered: weight 0
+    if (x < 0 || y < 0 || x >= (int)cam.width || y >= (int)cam.height) return r;
+    const uint32_t i = (uint32_t)x + (uint32_t)y * cam.width;
+    const size_t plane = (size_t)cam.width * cam.height;
+    if (FIRST) {
+        const float4 g2 = dp.guide[2u * plane + i];
+        if (!(g2.w > 0.0f)) return r;
+        uint32_t owner;
+        const uint32_t slot = pixel_to_slab(cam, (uint32_t)x, (uint32_t)y, owner);
+        const float4 a = dp.acc[(uint64_t)owner * dp.slab_elems + slot];
+        const float n = (float)(int)dp.samples;
+        r.x = make_float4((a.x * 1.0f / n) / gl_max(g2.x, kDnAlbedoFloor), (a.y * 1.0f / n) / gl_max(g2.y, kDnAlbedoFloor),
+                          (a.z * 1.0f / n) / gl_max(g2.z, kDnAlbedoFloor), 1.0f);
+    } else {
+        r.x = dp.in[i];
+        if (!(r.x.w > 0.0f)) return r;
+    }
+    r.g0 = dp.guide[i];
+    r.g1 = dp.guide[plane + i];
+    return r;
+}
+
+// sw += w(p, q), sx += w(p, q) x(q); inv_plane = 1 / (kDnPlane t_p)
+RFW_DI void dn_tap(const DnPixel& p, const float inv_plane, const float inv_sigma2, const float h, const float4 xq, const float4 g0q, const float4 g1q, float& sw,
+                   f3& sx)
+{
+    if (!(xq.w > 0.0f)) return;
+    float wn = gl_max(0.0f, p.g0.x * g0q.x + p.g0.y * g0q.y + p.g0.z * g0q.z);
+    for (int k = 0; k < kDnNormalSquarings; k++) wn = wn * wn;
+    const float d = p.g0.x * (g1q.x - p.g1.x) + p.g0.y * (g1q.y - p.g1.y) + p.g0.z * (g1q.z - p.g1.z);
+    const float wp = gl_max(0.0f, 1.0f - gl_abs(d) * inv_plane);
+    const float cx = p.x.x - xq.x, cy = p.x.y - xq.y, cz = p.x.z - xq.z;
+    const float d2 = cx * cx + cy * cy + cz * cz;
+    if (!(d2 < 3.0e38f)) return; // a tap that is not finite (a NaN or Inf accumulator pixel) stays where it is: it spoils its own pixel only
+    const float wc = rfw_expf(-(d2 * inv_sigma2));
+    const float w = h * wn * wp * wc;
+    sw += w;
+    sx = sx + w * mk3(xq.x, xq.y, xq.z);
+}
+
+template <bool FIRST, bool LAST, bool TILED>
+__global__ __launch_bounds__(kDnTile * kDnTile) void k_atrous(const CameraParams cam, const DnParams dp)
+{
+    const int shift = (int)dp.step_shift, s = 1 << shift;
+    const int lx = (int)(threadIdx.x % kDnTile), ly = (int)(threadIdx.x / kDnTile);
+    int px, py;
+    DnPixel c;
+    float sw = 0.0f;
+    f3 sx = mk3(0.0f);
+    if (TILED) {
+        __shared__ float4 s_x[kDnSpan * kDnPitch], s_g0[kDnSpan * kDnPitch], s_g1[kDnSpan * kDnPitch];
+        // sub-image (ox, oy) of the step, and the window's first pixel in sub-image coordinates
+        const int ox = (int)blockIdx.x & (s - 1), oy = (int)blockIdx.y & (s - 1);
+        const int i0 = (int)(blockIdx.x >> shift) * kDnTile - kDnRadius, j0 = (int)(blockIdx.y >> shift) * kDnTile - kDnRadius;
+        for (int k = (int)threadIdx.x; k < kDnSpan * kDnSpan; k += kDnTile * kDnTile) {
+            const int wx = k % kDnSpan, wy = k / kDnSpan;
+            const DnPixel q = dn_load<FIRST>(cam, dp, ox + (i0 + wx) * s, oy + (j0 + wy) * s); // (left of / above the frame: negative)
+            s_x[wy * kDnPitch + wx] = q.x;
+            s_g0[wy * kDnPitch + wx] = q.g0;
+            s_g1[wy * kDnPitch + wx] = q.g1;
+        }
+        __syncthreads();
+        px = ox + (i0 + kDnRadius + lx) * s;
+        py = oy + (j0 + kDnRadius + ly) * s;
+        if (px >= (int)cam.width || py >= (int)cam.height) return;
+        const int at = (ly + kDnRadius) * kDnPitch + lx + kDnRadius;
+        c.x = s_x[at]; c.g0 = s_g0[at]; c.g1 = s_g1[at];
+        if (c.x.w > 0.0f) {
+            const float inv_plane = 1.0f / (kDnPlane * c.g0.w);
+#pragma unroll
+            for (int dy = 0; dy <= 2 * kDnRadius; dy++)
+#pragma unroll
+                for (int dx = 0; dx <= 2 * kDnRadius; dx++) {
+                    const int k = (ly + dy) * kDnPitch + lx + dx;
+                    dn_tap(c, inv_plane, dp.inv_sigma2, kDnH[dx] * kDnH[dy], s_x[k], s_g0[k], s_g1[k], sw, sx);
+                }
+        }
+    } else {
+        px = (int)(blockIdx.x * kDnTile) + lx;
+        py = (int)(blockIdx.y * kDnTile) + ly;
+        if (px >= (int)cam.width || py >= (int)cam.height) return;
+        c = dn_load<FIRST>(cam, dp, px, py);
+        if (c.x.w > 0.0f) {
+            const float inv_plane = 1.0f / (kDnPlane * c.g0.w);
+            for (int dy = 0; dy <= 2 * kDnRadius; dy++)
+                for (int dx = 0; dx <= 2 * kDnRadius; dx++) {
+                    const DnPixel q = dn_load<FIRST>(cam, dp, px + (dx - kDnRadius) * s, py + (dy - kDnRadius) * s);
+                    dn_tap(c, inv_plane, dp.inv_sigma2, kDnH[dx] * kDnH[dy], q.x, q.g0, q.g1, sw, sx);
+                }
+        }
+    }
+    const bool filtered = c.x.w > 0.0f; // (then sw >= h(0)^2 wn(p, p) > 0: the centre tap — unless x(p) itself is not finite: 0 / 0, the pixel stays bad)
+    float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (filtered) out = make_float4(sx.x / sw, sx.y / sw, sx.z / sw, 1.0f);
+    const uint32_t i = (uint32_t)px + (uint32_t)py * cam.width;
+    if (LAST) {
+        uint32_t owner;
+        const uint32_t slot = pixel_to_slab(cam, (uint32_t)px, (uint32_t)py, owner);
+        const float4 a = dp.acc[(uint64_t)owner * dp.slab_elems + slot];
+        const float n = (float)(int)dp.samples;
+        if (filtered) {
+            const float4 g2 = dp.guide[2u * (size_t)cam.width * cam.height + i];
+            out.x = __builtin_sqrtf(out.x * gl_max(g2.x, kDnAlbedoFloor));
+            out.y = __builtin_sqrtf(out.y * gl_max(g2.y, kDnAlbedoFloor));
+            out.z = __builtin_sqrtf(out.z * gl_max(g2.z, kDnAlbedoFloor));
+        } else {
+            out.x = finalise<false>(a.x, n);
+            out.y = finalise<false>(a.y, n);
+            out.z = finalise<false>(a.z, n);
+        }
+        out.w = finalise<false>(a.w, n);
+    }
+    dp.out[i] = out;
+}
+
+void launch_dn_guide(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, float4* guide, uint32_t pixel_mask)
+{
+    if (p.capacity) hipLaunchKernelGGL(k_dn_guide, dim3((p.capacity + 255u) / 256u), dim3(256), 0, s, cam, sc, p, guide, pixel_mask);
+}
+
+template <bool TILED> static void launch_atrous_pass(hipStream_t s, const CameraParams& cam, const DnParams& dp, bool first, bool last)
+{
+    const uint32_t step = 1u << dp.step_shift;
+    // TILED: the tiles of one sub-image ((width / step) x (height / step) pixels, rounded up), times step^2 sub-images, those fastest
+    const dim3 grid = TILED ? dim3(ceil_div(ceil_div(cam.width, step), kDnTile) * step, ceil_div(ceil_div(cam.height, step), kDnTile) * step)
+                            : dim3(ceil_div(cam.width, kDnTile), ceil_div(cam.height, kDnTile));
+    const dim3 block(kDnTile * kDnTile);
+    if (first && last) hipLaunchKernelGGL((k_atrous<true, true, TILED>), grid, block, 0, s, cam, dp);
+    else if (first) hipLaunchKernelGGL((k_atrous<true, false, TILED>), grid, block, 0, s, cam, dp);
+    else if (last) hipLaunchKernelGGL((k_atrous<false, true, TILED>), grid, block, 0, s, cam, dp);
+    else hipLaunchKernelGGL((k_atrous<false, false, TILED>), grid, block, 0, s, cam, dp);
+}
+
+void launch_atrous(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, float4* const planes[2], float4* frame,
+                   uint32_t samples, uint32_t passes, float sigma_colour, uint32_t form)
+{
+    for (uint32_t i = 0; i < passes; i++) {
+        DnParams dp;
+        dp.acc = acc;
+        dp.slab_elems = slab_elems;
+        dp.guide = guide;
+        dp.in = i ? planes[(i - 1u) & 1u] : nullptr;
+        dp.out = i + 1u == passes ? frame : planes[i & 1u];
+        dp.samples = samples;
+        dp.step_shift = i;
+        const float sigma = (float)((double)sigma_colour / (double)(1u << i) / std::sqrt((double)samples));
+        dp.inv_sigma2 = (float)std::min(1.0 / ((double)sigma * (double)sigma), 3.0e38); // (finite: 0 x inf would poison equal colours)
+        const bool tiled = form == 0u ? atrous_tiled_by_default(i) : form == 2u;
+        if (tiled) launch_atrous_pass<true>(s, cam, dp, i == 0u, i + 1u == passes);
+        else launch_atrous_pass<false>(s, cam, dp, i == 0u, i + 1u == passes);
+    }
+}

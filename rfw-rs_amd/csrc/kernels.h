@@ -110,6 +110,15 @@ void launch_aov(hipStream_t s, const CameraParams& cam, const SceneDev& sc, cons
                 const float direction[3]);
 // mode 6 where the frame is de-tiled on this device: the edge-aware filter of acc.x / samples (slabs of slab_elems, as launch_assemble) into `frame`
 void launch_ao_filter(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, float4* frame, uint32_t samples);
+// option "denoise" (denoise.inc).  Guide: after the primary launch and BEFORE launch_shade, three planes of width x height per frame pixel,
+// (faced gN, t), (P, 0), (albedo, f); `pixel_mask` strips the sample index a batch of samples keeps above the pixel index of the path word.
+void launch_dn_guide(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, float4* guide, uint32_t pixel_mask);
+// `passes` (1 .. kDenoiseMaxPasses) a-trous passes from the accumulator slabs (as launch_assemble reads them) into `frame`, in place of
+// launch_assemble; planes[2]: width x height each, used when passes > 1.  form: 0 = the form measured to be faster per step, 1 direct, 2 tiled.
+constexpr uint32_t kDenoiseMaxPasses = 5;
+constexpr float kDenoiseDefaultColour = 32.0f; // option "denoise_colour" (sigma_c, demodulated radiance): chosen by the sweep in DESIGN.md "Denoiser"
+void launch_atrous(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, float4* const planes[2], float4* frame,
+                   uint32_t samples, uint32_t passes, float sigma_colour, uint32_t form);
 void launch_eval_shading(hipStream_t s, const SceneDev& sc, const CameraParams& cam, int op, uint32_t n, const float* in, float* out);
 void launch_query_closest(hipStream_t s, const SceneDev& sc, const float* origins, const float* directions, float t_min, float t_max, uint64_t n,
                           rfw_hip_hit* hits, uint32_t* depth = nullptr /* optional: nodes visited per ray */);

@@ -1589,5 +1589,7 @@ void launch_query_any(hipStream_t s, const SceneDev& sc, const float* origins, c
 
 // ---------------------------------------------------------------- render modes 1-6 (rfw_hip_render's `mode`)
 #include "aov.inc"
+// ---------------------------------------------------------------- option "denoise": the guided a-trous filter of the path-traced frame
+#include "denoise.inc"
 
 } // namespace rfwhip

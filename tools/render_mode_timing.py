@@ -3,7 +3,11 @@
 
 One instance, one frame at a time: every repeat renders `--frames` frames of the same view and then reads the framebuffer back (the wait),
 after `--warmup` frames.  Prints one line per mode with the median, min and max of the repeats' ms per frame.  DESIGN.md "Render modes"
-quotes its output."""
+quotes its output.
+
+--denoise 0,1,3,5 times mode 0 under option "denoise" instead (DESIGN.md "Denoiser"): the settings take turns, repeat by repeat, so that
+they share whatever else the machine is doing; --denoise-form 1 / 2 forces the direct / tiled kernel form; --bandwidth adds what
+rfw_hip_bandwidth_probe reads per second, the yardstick of a pass's 64 algorithmic bytes per pixel."""
 import argparse
 import os
 import statistics
@@ -16,6 +20,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--modes", default="0,5,6")
+    ap.add_argument("--denoise", default="")
+    ap.add_argument("--denoise-form", type=int, default=0)
+    ap.add_argument("--max-path-length", type=int, default=None)  # 1 for the modes (DESIGN.md "Render modes"), 3 with --denoise
+    ap.add_argument("--bandwidth", action="store_true")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--triangles", type=int, default=1048576)  # bench.py's atrium1m
@@ -24,14 +32,38 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
+    if a.max_path_length is None:
+        a.max_path_length = 3 if a.denoise else 1
     import torch  # (the order bench.py has: torch's HIP runtime first)
     torch.cuda.init()
     from rfw_rs_amd import HipBackend, RenderMode, Scene
     scene = Scene().build("atrium", a.triangles, 0, 0.0, 0xC0FFEE)
     scene.set_aspect(a.width / a.height)
     view = scene.view(a.width, a.height)
-    be = HipBackend.init(a.width, a.height, 1.0, max_path_length=1)
+    be = HipBackend.init(a.width, a.height, 1.0, max_path_length=a.max_path_length)
     scene.sync(be)
+    what = f"{a.repeats} x {a.frames} frames, {a.width}x{a.height}, atrium of {a.triangles} triangles, max path length {a.max_path_length}"
+    if a.denoise:
+        settings = [int(k) for k in a.denoise.split(",")]
+        if any(settings):
+            be.set_option("denoise_form", a.denoise_form)
+        runs = {k: [] for k in settings}
+        for rep in range(-1, a.repeats):  # (-1: the warm-up round of every setting)
+            for k in settings:
+                if any(settings):  # (all zero: never name the option, so that a library without it can be timed too)
+                    be.set_option("denoise", k)
+                t0 = time.perf_counter()
+                for _ in range(a.warmup if rep < 0 else a.frames):
+                    be.render(view)
+                be.framebuffer()
+                if rep >= 0:
+                    runs[k].append((time.perf_counter() - t0) * 1e3 / a.frames)
+        for k in settings:
+            print(f"denoise {k} form {a.denoise_form}: {statistics.median(runs[k]):.3f} ms/frame (min {min(runs[k]):.3f}, max {max(runs[k]):.3f}; {what})", flush=True)
+        if a.bandwidth:
+            print(f"bandwidth probe: {be.bandwidth_probe():.0f} GB/s (read + written); a pass moves 64 B x {a.width * a.height} pixels = {64e-6 * a.width * a.height:.1f} MB", flush=True)
+        be.close()
+        return
     be.set_option("ao_samples", a.ao_samples)
     for mode in (RenderMode(int(m)) for m in a.modes.split(",")):
         for _ in range(a.warmup):
@@ -44,8 +76,8 @@ def main():
                 be.render(view, mode=mode)
             be.framebuffer()
             runs.append((time.perf_counter() - t0) * 1e3 / a.frames)
-        print(f"mode {int(mode)} {mode.name}: {statistics.median(runs):.3f} ms/frame (min {min(runs):.3f}, max {max(runs):.3f}; {a.repeats} x {a.frames} "
-              f"frames, {a.width}x{a.height}, atrium of {a.triangles} triangles, ao_samples {a.ao_samples}, max path length 1)", flush=True)
+        print(f"mode {int(mode)} {mode.name}: {statistics.median(runs):.3f} ms/frame (min {min(runs):.3f}, max {max(runs):.3f}; {what}, "
+              f"ao_samples {a.ao_samples})", flush=True)
     be.close()
 
 
