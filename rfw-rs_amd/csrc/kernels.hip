@@ -13,6 +13,8 @@
 #include "traverse.h"
 #include "traverse_packet.h"
 
+#include <type_traits>
+
 // waves per SIMD the trace kernels are compiled for (register budget 512 / waves), chosen by measurement with frames in flight:
 // closest hit (k_primary, k_extend) 6 (5: -6 %, 7: -2 %, 8: -11 %); any hit (k_shadow: fewer live values) 8 (7: -1.4 %, 6: -2.8 %)
 // the streaming flavours alike; the packet kernels 8 (6 -> 6755, 7 -> 6785, 8 -> 6855 Mrays/s: 16 spilled registers at 8 cost less than the two extra waves hide)
@@ -272,145 +274,115 @@ RFW_DI uint32_t xcd_run(const uint32_t b, const uint32_t per_tile)
 }
 
 // ---------------------------------------------------------------- ray_gen.comp:39-70
-template <bool COUNT> __global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_primary(const CameraParams cam, const SceneDev sc, const PathDev p)
+// The hit record of the wavefront state (kernels.h: inst, tri, bits(t), barycentrics as 16:16 fixed point)
+RFW_DI uint4 pack_hit(const int32_t hi, const int32_t ht, const float t, const float hu, const float hv)
+{
+    const uint32_t bary = f2u(65535.0f * hu) + (f2u(65535.0f * hv) << 16);
+    return make_uint4((uint32_t)hi, (uint32_t)ht, fbits(t), bary);
+}
+
+// What the k_primary* kernels do before the trace, in two steps.  First: slab slot idx -> its pixel; `valid` where it holds one, `in_slab` where
+// the slot exists at all.  BATCH (rfw_hip_render_batch): the slots of every frame of the batch follow each other, `f` is the slot's frame.
+struct CameraSlot {
+    uint32_t px, py, f;
+    bool in_slab, valid;
+};
+template <bool BATCH> RFW_DI CameraSlot camera_slot(const CameraParams& cam, const PathDev& p, const uint32_t block, const uint32_t idx)
+{
+    CameraSlot cs{0u, 0u, 0u, false, false};
+    if (BATCH) cs.f = (block * kTraceBlock) / cam.frame_capacity; // uniform: a frame's range is a multiple of the workgroup size
+    cs.in_slab = BATCH ? cs.f < cam.batch : idx < p.capacity;
+    cs.valid = cs.in_slab && slab_to_pixel(cam, idx - cs.f * cam.frame_capacity, cs.px, cs.py);
+    return cs;
+}
+// Then, for a valid slot: clear the accumulator where the image starts, draw the camera ray and store it.  A frame of a batch has its view and
+// sample index from `views` / cam.batch_sample, and its index rides in the top byte of the path word.
+template <bool BATCH>
+RFW_DI void begin_camera_path(const CameraParams& cam, const BatchViews* views, const SceneDev& sc, const PathDev& p, const uint32_t idx, const CameraSlot& cs, f3& O, f3& D)
+{
+    const uint32_t sample = BATCH ? cam.batch_sample[cs.f] : cam.sample_count;
+    // a batch of new images clears every frame; a batch of SAMPLES of one image (rfw_hip_render_samples) keeps what frame 0 has
+    // accumulated so far (sample_count = samples already in the image)
+    if (BATCH ? !(cs.f == 0u && cam.sample_count != 0u) : cam.sample_count == 0) p.acc[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    CameraParams c = cam;
+    if (BATCH) {
+        const FrameView& v = views->v[cs.f];
+        for (int k = 0; k < 3; k++) { c.pos[k] = v.pos[k]; c.right[k] = v.right[k]; c.up[k] = v.up[k]; c.p1[k] = v.p1[k]; }
+        c.lens_size = v.lens_size;
+    }
+    const uint32_t path_id = cs.px + cs.py * cam.width;
+    uint32_t seed = wang_hash(path_id * 16789u + sample * 1791u + 0u * 720898027u);
+    generate_eye_ray(c, O, D, cs.px, cs.py, seed, sc.blue_noise, sample);
+    p.ray_o[0][idx] = make_float4(O.x, O.y, O.z, bitsf(BATCH ? path_id | (cs.f << 24) : path_id)); // before the trace: the ray need not stay live across it
+    p.ray_d[0][idx] = make_float4(D.x, D.y, D.z, 0.0f);
+}
+// ... and for a slab slot without a pixel (ragged edge tile): k_shade skips it without redoing the index arithmetic
+RFW_DI void mark_no_path(const PathDev& p, const uint32_t idx, const CameraSlot& cs)
+{
+    if (cs.in_slab) p.hit[0][idx] = make_uint4(kNoPath, 0u, 0u, 0u);
+}
+// One ray per lane: only the lanes that hold a pixel trace.  (What such a lane does stays in ONE branch: with the set-up, the trace and the hit
+// store under a condition each, the compiler keeps three regions: k_primary<false> 812 -> 816 vector, 441 -> 447 scalar instructions.)
+template <bool COUNT, bool BATCH>
+RFW_DI void primary_per_lane(const CameraParams& cam, const BatchViews* views, const SceneDev& sc, const PathDev& p)
 {
     clear_next_counters(sc);
     __shared__ uint32_t s_stack[kTraceLdsRows * kTraceBlock];
     const uint32_t block = xcd_block(blockIdx.x);
     const uint32_t idx = block * kTraceBlock + threadIdx.x;
     TravCounters tc{0, 0, 0};
-    uint32_t px = 0, py = 0;
-    const bool valid = idx < p.capacity && slab_to_pixel(cam, idx, px, py);
-    if (valid) {
-        if (cam.sample_count == 0) p.acc[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        const uint32_t path_id = px + py * cam.width;
-        uint32_t seed = wang_hash(path_id * 16789u + cam.sample_count * 1791u + 0u * 720898027u);
+    const CameraSlot cs = camera_slot<BATCH>(cam, p, block, idx);
+    if (cs.valid) {
         f3 O, D;
-        generate_eye_ray(cam, O, D, px, py, seed, sc.blue_noise, cam.sample_count);
+        begin_camera_path<BATCH>(cam, views, sc, p, idx, cs, O, D);
         float t = 1e26f, hu = 0.0f, hv = 0.0f;
         int32_t hi = -1, ht = -1;
-        const SceneView sv = scene_view(sc);
-        p.ray_o[0][idx] = make_float4(O.x, O.y, O.z, bitsf(path_id)); // before the trace: the ray need not stay live across it
-        p.ray_d[0][idx] = make_float4(D.x, D.y, D.z, 0.0f);
-        traverse<false, COUNT>(sv, O, D, 1e-4f, t, hu, hv, hi, ht, s_stack, threadIdx.x, block * kTraceBlock, tc);
-        const uint32_t bary = f2u(65535.0f * hu) + (f2u(65535.0f * hv) << 16);
-        p.hit[0][idx] = make_uint4((uint32_t)hi, (uint32_t)ht, fbits(t), bary);
-    } else if (idx < p.capacity) {
-        p.hit[0][idx] = make_uint4(kNoPath, 0u, 0u, 0u); // a slab slot without a pixel (ragged edge tile): k_shade skips it without redoing the index arithmetic
-    }
+        traverse<false, COUNT>(scene_view(sc), O, D, 1e-4f, t, hu, hv, hi, ht, s_stack, threadIdx.x, block * kTraceBlock, tc);
+        p.hit[0][idx] = pack_hit(hi, ht, t, hu, hv);
+    } else mark_no_path(p, idx, cs);
     flush_counters<COUNT>(sc.counters, tc, 0);
 }
-
-// The packet flavour (traverse_packet.h): the 64 camera rays of an 8x8-pixel block walk the tree together on one shared stack.  Same rays,
-// same triangle tests, same image; no LDS.
-template <bool COUNT> __global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_primary_packet(const CameraParams cam, const SceneDev sc, const PathDev p)
+// The packet flavour (traverse_packet.h): the 64 camera rays of an 8x8-pixel block walk the tree together on one shared stack, the lanes without a
+// pixel idle among them.  Same rays, same triangle tests, same image; no LDS.
+template <bool COUNT, bool BATCH>
+RFW_DI void primary_packet(const CameraParams& cam, const BatchViews* views, const SceneDev& sc, const PathDev& p)
 {
     clear_next_counters(sc);
     const uint32_t block = xcd_block(blockIdx.x);
     const uint32_t idx = block * kTraceBlock + threadIdx.x;
     TravCounters tc{0, 0, 0};
-    uint32_t px = 0, py = 0;
-    const bool valid = idx < p.capacity && slab_to_pixel(cam, idx, px, py);
+    const CameraSlot cs = camera_slot<BATCH>(cam, p, block, idx);
     f3 O = mk3(0.0f), D = mk3(0.0f);
-    if (valid) {
-        if (cam.sample_count == 0) p.acc[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        const uint32_t path_id = px + py * cam.width;
-        uint32_t seed = wang_hash(path_id * 16789u + cam.sample_count * 1791u + 0u * 720898027u);
-        generate_eye_ray(cam, O, D, px, py, seed, sc.blue_noise, cam.sample_count);
-        p.ray_o[0][idx] = make_float4(O.x, O.y, O.z, bitsf(path_id));
-        p.ray_d[0][idx] = make_float4(D.x, D.y, D.z, 0.0f);
-    }
+    if (cs.valid) begin_camera_path<BATCH>(cam, views, sc, p, idx, cs, O, D);
     float t = 1e26f, hu = 0.0f, hv = 0.0f;
     int32_t hi = -1, ht = -1;
     bool occluded;
     const SceneView sv = scene_view(sc);
-    traverse_packet<false, COUNT>(sv, sc.tlas_wide, sc.tlas_wide_stride, sc.blas_wide, sc.blas_wide_stride, valid, O, D, 1e-4f, t, hu, hv, hi, ht, occluded, tc);
-    if (valid) {
-        const uint32_t bary = f2u(65535.0f * hu) + (f2u(65535.0f * hv) << 16);
-        p.hit[0][idx] = make_uint4((uint32_t)hi, (uint32_t)ht, fbits(t), bary);
-    } else if (idx < p.capacity) {
-        p.hit[0][idx] = make_uint4(kNoPath, 0u, 0u, 0u);
-    }
+    traverse_packet<false, COUNT>(sv, sc.tlas_wide, sc.tlas_wide_stride, sc.blas_wide, sc.blas_wide_stride, cs.valid, O, D, 1e-4f, t, hu, hv, hi, ht, occluded, tc);
+    if (cs.valid) p.hit[0][idx] = pack_hit(hi, ht, t, hu, hv);
+    else mark_no_path(p, idx, cs);
     flush_counters<COUNT>(sc.counters, tc, 0);
 }
 
-// the same for a batch of independent frames (rfw_hip_render_batch): one launch covers the tiles of every frame of the batch
+template <bool COUNT> __global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_primary(const CameraParams cam, const SceneDev sc, const PathDev p)
+{
+    primary_per_lane<COUNT, false>(cam, nullptr, sc, p);
+}
+template <bool COUNT> __global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_primary_packet(const CameraParams cam, const SceneDev sc, const PathDev p)
+{
+    primary_packet<COUNT, false>(cam, nullptr, sc, p);
+}
+// the same for a batch of independent frames (rfw_hip_render_batch): one launch covers the tiles of every frame of the batch.  A wavefront's 64
+// paths belong to ONE frame, so for the packet flavour they are one 8x8-pixel block of one view as in k_primary_packet
 template <bool COUNT>
 __global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_primary_batch(const CameraParams cam, const BatchViews views, const SceneDev sc, const PathDev p)
 {
-    clear_next_counters(sc);
-    __shared__ uint32_t s_stack[kTraceLdsRows * kTraceBlock];
-    const uint32_t block = xcd_block(blockIdx.x);
-    const uint32_t idx = block * kTraceBlock + threadIdx.x;
-    const uint32_t f = (block * kTraceBlock) / cam.frame_capacity; // uniform: a frame's range is a multiple of the workgroup size
-    TravCounters tc{0, 0, 0};
-    uint32_t px = 0, py = 0;
-    const bool valid = f < cam.batch && slab_to_pixel(cam, idx - f * cam.frame_capacity, px, py);
-    if (valid) {
-        const uint32_t sample = cam.batch_sample[f];
-        // a batch of new images clears every frame; a batch of SAMPLES of one image (rfw_hip_render_samples) keeps what frame 0 has
-        // accumulated so far (sample_count = samples already in the image)
-        if (!(f == 0u && cam.sample_count != 0u)) p.acc[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        CameraParams c = cam;
-        const FrameView& v = views.v[f];
-        for (int k = 0; k < 3; k++) { c.pos[k] = v.pos[k]; c.right[k] = v.right[k]; c.up[k] = v.up[k]; c.p1[k] = v.p1[k]; }
-        c.lens_size = v.lens_size;
-        const uint32_t path_id = px + py * cam.width;
-        uint32_t seed = wang_hash(path_id * 16789u + sample * 1791u + 0u * 720898027u);
-        f3 O, D;
-        generate_eye_ray(c, O, D, px, py, seed, sc.blue_noise, sample);
-        float t = 1e26f, hu = 0.0f, hv = 0.0f;
-        int32_t hi = -1, ht = -1;
-        const SceneView sv = scene_view(sc);
-        p.ray_o[0][idx] = make_float4(O.x, O.y, O.z, bitsf(path_id | (f << 24)));
-        p.ray_d[0][idx] = make_float4(D.x, D.y, D.z, 0.0f);
-        traverse<false, COUNT>(sv, O, D, 1e-4f, t, hu, hv, hi, ht, s_stack, threadIdx.x, block * kTraceBlock, tc);
-        const uint32_t bary = f2u(65535.0f * hu) + (f2u(65535.0f * hv) << 16);
-        p.hit[0][idx] = make_uint4((uint32_t)hi, (uint32_t)ht, fbits(t), bary);
-    } else if (f < cam.batch) {
-        p.hit[0][idx] = make_uint4(kNoPath, 0u, 0u, 0u);
-    }
-    flush_counters<COUNT>(sc.counters, tc, 0);
+    primary_per_lane<COUNT, true>(cam, &views, sc, p);
 }
-
-// ... and the packet flavour for a batch of frames: a wavefront's 64 paths belong to ONE frame (a frame's range is a multiple of the workgroup
-// size), so they are one 8x8-pixel block of one view as in k_primary_packet
 template <bool COUNT>
 __global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_primary_batch_packet(const CameraParams cam, const BatchViews views, const SceneDev sc, const PathDev p)
 {
-    clear_next_counters(sc);
-    const uint32_t block = xcd_block(blockIdx.x);
-    const uint32_t idx = block * kTraceBlock + threadIdx.x;
-    const uint32_t f = (block * kTraceBlock) / cam.frame_capacity;
-    TravCounters tc{0, 0, 0};
-    uint32_t px = 0, py = 0;
-    const bool valid = f < cam.batch && slab_to_pixel(cam, idx - f * cam.frame_capacity, px, py);
-    f3 O = mk3(0.0f), D = mk3(0.0f);
-    if (valid) {
-        const uint32_t sample = cam.batch_sample[f];
-        if (!(f == 0u && cam.sample_count != 0u)) p.acc[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        CameraParams c = cam;
-        const FrameView& v = views.v[f];
-        for (int k = 0; k < 3; k++) { c.pos[k] = v.pos[k]; c.right[k] = v.right[k]; c.up[k] = v.up[k]; c.p1[k] = v.p1[k]; }
-        c.lens_size = v.lens_size;
-        const uint32_t path_id = px + py * cam.width;
-        uint32_t seed = wang_hash(path_id * 16789u + sample * 1791u + 0u * 720898027u);
-        generate_eye_ray(c, O, D, px, py, seed, sc.blue_noise, sample);
-        p.ray_o[0][idx] = make_float4(O.x, O.y, O.z, bitsf(path_id | (f << 24)));
-        p.ray_d[0][idx] = make_float4(D.x, D.y, D.z, 0.0f);
-    }
-    float t = 1e26f, hu = 0.0f, hv = 0.0f;
-    int32_t hi = -1, ht = -1;
-    bool occluded;
-    const SceneView sv = scene_view(sc);
-    traverse_packet<false, COUNT>(sv, sc.tlas_wide, sc.tlas_wide_stride, sc.blas_wide, sc.blas_wide_stride, valid, O, D, 1e-4f, t, hu, hv, hi, ht, occluded, tc);
-    if (valid) {
-        const uint32_t bary = f2u(65535.0f * hu) + (f2u(65535.0f * hv) << 16);
-        p.hit[0][idx] = make_uint4((uint32_t)hi, (uint32_t)ht, fbits(t), bary);
-    } else if (f < cam.batch) {
-        p.hit[0][idx] = make_uint4(kNoPath, 0u, 0u, 0u);
-    }
-    flush_counters<COUNT>(sc.counters, tc, 0);
+    primary_packet<COUNT, true>(cam, &views, sc, p);
 }
 
 // ---------------------------------------------------------------- extension rays in spatial order (option "sort_extension_rays")
@@ -469,8 +441,7 @@ __global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_extend(const Camer
         int32_t hi = -1, ht = -1;
         const SceneView sv = scene_view(sc);
         traverse<false, COUNT>(sv, O, D, 1e-4f, t, hu, hv, hi, ht, s_stack, threadIdx.x, block * kTraceBlock, tc);
-        const uint32_t bary = f2u(65535.0f * hu) + (f2u(65535.0f * hv) << 16);
-        p.hit[half][j] = make_uint4((uint32_t)hi, (uint32_t)ht, fbits(t), bary);
+        p.hit[half][j] = pack_hit(hi, ht, t, hu, hv);
     }
     flush_counters<COUNT>(sc.counters, tc, 1);
 }
@@ -496,11 +467,7 @@ struct ExtendStream {
         return true;
     }
     RFW_DI void advance(const uint64_t idle) { next += (uint32_t)__popcll(idle); }
-    RFW_DI void commit(bool, const float t, const float hu, const float hv, const int32_t hi, const int32_t ht)
-    {
-        const uint32_t bary = f2u(65535.0f * hu) + (f2u(65535.0f * hv) << 16);
-        p.hit[half][j] = make_uint4((uint32_t)hi, (uint32_t)ht, fbits(t), bary);
-    }
+    RFW_DI void commit(bool, const float t, const float hu, const float hv, const int32_t hi, const int32_t ht) { p.hit[half][j] = pack_hit(hi, ht, t, hu, hv); }
 };
 template <bool COUNT>
 __global__ __launch_bounds__(kTraceBlock, kStreamWaves) void k_extend_stream(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce,
@@ -519,48 +486,86 @@ __global__ __launch_bounds__(kTraceBlock, kStreamWaves) void k_extend_stream(con
 }
 
 // ---------------------------------------------------------------- ray_shadow.comp:245-268
+// Rays towards a directional light leave the scene: what blocks the sky is most often the LAST thing on their way (roofs, upper
+// floors), so their occluder search starts at the far end (measured on the bench scene's real shadow queue: 21.6 -> 12.1 nodes per
+// ray; rays towards the area lights get up to 15 % longer that way and keep the near-to-far order).  shade files every directional
+// light's rays under the last bucket, so the bucket tells the kind of light.
+RFW_DI bool bucket_far_first(const CameraParams& cam, const uint32_t bucket)
+{
+    return bucket == (uint32_t)kShadowBuckets - 1u ? !(cam.flags & kFlagNearFirstDirectional) : (cam.flags & kFlagFarFirstPositional) != 0u; // option "shadow_order" overrides the default per light kind
+}
+// The queue is bucketed by light (shade pushes directional lights into the last region, positional lights into region light % 7), each bucket padded
+// to whole launch blocks of per_block entries, so the 64 rays of a wavefront start on neighbouring pixels AND aim at the same light.  Launch block
+// `block` -> the bucket it falls into, that bucket's entry count and the block's index inside the bucket; !found: behind the last bucket.
 // Buckets are walked from the LAST light index down (directional lights come last in the reference's light order, shade.comp:471-527): a
 // measured choice — k_shadow alone 0.364 -> 0.336 ms when it was made, 0.382 -> 0.329 ms with the far-to-near order of the directional
-// light's rays below; with frames in flight the order of the buckets does not matter.
-RFW_DI bool bucket_far_first(const CameraParams& cam, const uint32_t bucket);
+// light's rays; with frames in flight the order of the buckets does not matter.  skip(k): bucket k belongs to another launch.
+// (The result travels by value: with block / bucket / count as reference parameters the compiler turns the walk's branches into selects —
+// k_shadow 803 -> 788, k_shadow_packet 470 -> 454, k_shadow_stream 646 -> 651 scalar instructions; this form compiles to what the three written-out loops did.)
+struct ShadowBucket {
+    bool found;
+    uint32_t bucket, count, block;
+};
+template <class Skip> RFW_DI ShadowBucket find_shadow_bucket(const SceneDev& sc, const uint32_t bounce, const uint32_t per_block, uint32_t block, const Skip skip)
+{
+    uint32_t bucket = 0, count = 0;
+    bool found = false;
+    for (int kk = 0; kk < kShadowBuckets; kk++) {
+        const int k = kShadowBuckets - 1 - kk;
+        if (skip((uint32_t)k)) continue;
+        const uint32_t c = sc.counters->shadow[bounce][k];
+        const uint32_t nb = (c + per_block - 1u) / per_block;
+        if (!found) {
+            if (block < nb) { found = true; bucket = (uint32_t)k; count = c; }
+            else block -= nb;
+        }
+    }
+    return {found, bucket, count, block};
+}
+RFW_DI void load_shadow_ray(const PathDev& p, const uint32_t idx, f3& O, f3& D, float& t)
+{
+    const float4 o4 = p.sh_o[idx], d4 = p.sh_d[idx];
+    O = mk3(o4.x, o4.y, o4.z);
+    D = mk3(d4.x, d4.y, d4.z);
+    t = d4.w - 0.0001f;
+    if (t > 3.0e38f) t = 3.0e38f; // a light at infinite distance (see k_query_closest)
+}
+// an unoccluded shadow ray adds what its queue entry carries
+RFW_DI void add_contribution(const PathDev& p, const uint32_t idx)
+{
+    const float4 e = p.sh_e[idx];
+    const uint32_t slot = fbits(e.w); // the path's accumulator slot rides in the queue entry (k_shade knows it without arithmetic)
+    // single writer per pixel per pass (one shadow ray per path per bounce, whichever lane traces it), as ray_shadow.comp:268
+    float4 a = p.acc[slot];
+    a.x += e.x; a.y += e.y; a.z += e.z; a.w += 0.0f;
+    p.acc[slot] = a;
+}
+
+// (BATCH is not read: a batch needs nothing special here, the queue entry carries the accumulator slot.  Both twins are launched and pinned by
+// tests/test_render_modes_on_cpu.py, so the parameter stays.)
 template <bool COUNT, bool BATCH = false>
 __global__ __launch_bounds__(kTraceBlock, kTraceWavesAny) void k_shadow(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
 {
     __shared__ uint32_t s_stack[kTraceLdsRowsAny * kTraceBlock];
-    // the queue is bucketed by light (shade pushes directional lights into the last region, positional lights into region light % 7): walk the buckets, each padded to whole wavefronts, so
-    // the 64 rays of a wavefront start on neighbouring pixels AND aim at the same light
-    uint32_t block = xcd_block(blockIdx.x);
-    const uint32_t spill_base = block * kTraceBlock; // (of the launch index's block: unique per wavefront, whatever bucket it lands in)
-    uint32_t bucket = 0, count = 0;
-    {
-        bool found = false;
-        for (int kk = 0; kk < kShadowBuckets; kk++) {
-            const int k = kShadowBuckets - 1 - kk;
-            if ((cam.flags & kFlagPacketShadowFar) && bucket_far_first(cam, (uint32_t)k)) continue; // (those went as packets: launch_shadow)
-            const uint32_t c = sc.counters->shadow[bounce][k];
-            const uint32_t nb = (c + kTraceBlock - 1) / kTraceBlock;
-            if (!found) {
-                if (block < nb) { found = true; bucket = (uint32_t)k; count = c; }
-                else block -= nb;
-            }
-        }
-        if (!found) return;
-    }
+    const uint32_t launch_block = xcd_block(blockIdx.x);
+    const bool far_as_packets = (cam.flags & kFlagPacketShadowFar) != 0u; // (launch_shadow)
+    const ShadowBucket b = find_shadow_bucket(sc, bounce, kTraceBlock, launch_block, [&](const uint32_t k) { return far_as_packets && bucket_far_first(cam, k); });
+    // (of the launch index's block: unique per wavefront, whatever bucket it lands in.  Formed HERE, between the walk and its early return: formed
+    // before the walk, the compiler folds the walk's last step into the return, lays the blocks of the traversal loop out in another order and
+    // spends one scalar instruction more)
+    const uint32_t spill_base = launch_block * kTraceBlock;
+    if (!b.found) return;
+    const uint32_t bucket = b.bucket, count = b.count, block = b.block;
     const uint32_t local = block * kTraceBlock + threadIdx.x;
     const uint32_t idx = bucket * p.capacity + local;
     TravCounters tc{0, 0, 0};
     if (local < count) {
-        const float4 o4 = p.sh_o[idx], d4 = p.sh_d[idx];
-        const f3 O = mk3(o4.x, o4.y, o4.z), D = mk3(d4.x, d4.y, d4.z);
-        float t = d4.w - 0.0001f, hu, hv;
-        if (t > 3.0e38f) t = 3.0e38f; // a light at infinite distance (see k_query_closest)
+        f3 O, D;
+        float t, hu, hv;
+        load_shadow_ray(p, idx, O, D, t);
         int32_t hi = -1, ht = -1;
         const SceneView sv = scene_view(sc);
-        // Rays towards a directional light leave the scene: what blocks the sky is most often the LAST thing on their way (roofs, upper
-        // floors), so their occluder search starts at the far end (measured on the bench scene's real shadow queue: 21.6 -> 12.1 nodes per
-        // ray; rays towards the area lights get up to 15 % longer that way and keep the near-to-far order).  shade files every directional
-        // light's rays under the last bucket, so the bucket tells the kind of light.
-        const bool far_first = bucket == (uint32_t)kShadowBuckets - 1u ? !(cam.flags & kFlagNearFirstDirectional) : (cam.flags & kFlagFarFirstPositional) != 0u; // option "shadow_order" overrides the default per light kind
+        const bool far_first = bucket_far_first(cam, bucket);
         const bool occluded = far_first ? traverse<true, COUNT, true>(sv, O, D, 0.001f, t, hu, hv, hi, ht, s_stack, threadIdx.x, spill_base, tc)
                                         : traverse<true, COUNT, false>(sv, O, D, 0.001f, t, hu, hv, hi, ht, s_stack, threadIdx.x, spill_base, tc);
         if (!occluded) {
@@ -568,12 +573,7 @@ __global__ __launch_bounds__(kTraceBlock, kTraceWavesAny) void k_shadow(const Ca
             // pair that went to scratch memory at 8 waves per SIMD)
             uint32_t lane = threadIdx.x;
             asm volatile("" : "+v"(lane));
-            const float4 e = p.sh_e[bucket * p.capacity + block * kTraceBlock + lane];
-            const uint32_t slot = fbits(e.w); // the path's accumulator slot rides in the queue entry (k_shade knows it without arithmetic)
-            // single writer per pixel per pass (one shadow ray per path per bounce), as ray_shadow.comp:268
-            float4 a = p.acc[slot];
-            a.x += e.x; a.y += e.y; a.z += e.z; a.w += 0.0f;
-            p.acc[slot] = a;
+            add_contribution(p, bucket * p.capacity + block * kTraceBlock + lane);
         }
     }
     flush_counters<COUNT>(sc.counters, tc, 2);
@@ -581,50 +581,23 @@ __global__ __launch_bounds__(kTraceBlock, kTraceWavesAny) void k_shadow(const Ca
 
 // The packet flavour for the camera paths' shadow rays (bounce 0): the 64 rays of a wavefront start on neighbouring pixels and aim at one
 // light.  One instantiation per visiting order, each launch walking the buckets of its order (as the streaming flavour below).
-RFW_DI bool bucket_far_first(const CameraParams& cam, const uint32_t bucket);
 template <bool COUNT, bool FAR>
 __global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_shadow_packet(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
 {
-    uint32_t block = xcd_block(blockIdx.x);
-    uint32_t bucket = 0, count = 0;
-    {
-        bool found = false;
-        for (int kk = 0; kk < kShadowBuckets; kk++) {
-            const int k = kShadowBuckets - 1 - kk;
-            if (bucket_far_first(cam, (uint32_t)k) != FAR) continue;
-            const uint32_t c = sc.counters->shadow[bounce][k];
-            const uint32_t nb = (c + kTraceBlock - 1) / kTraceBlock;
-            if (!found) {
-                if (block < nb) { found = true; bucket = (uint32_t)k; count = c; }
-                else block -= nb;
-            }
-        }
-        if (!found) return;
-    }
-    const uint32_t local = block * kTraceBlock + threadIdx.x;
-    const uint32_t idx = bucket * p.capacity + local;
+    const ShadowBucket b = find_shadow_bucket(sc, bounce, kTraceBlock, xcd_block(blockIdx.x), [&](const uint32_t k) { return bucket_far_first(cam, k) != FAR; });
+    if (!b.found) return;
+    const uint32_t local = b.block * kTraceBlock + threadIdx.x;
+    const uint32_t idx = b.bucket * p.capacity + local;
     TravCounters tc{0, 0, 0};
-    const bool valid = local < count;
+    const bool valid = local < b.count;
     f3 O = mk3(0.0f), D = mk3(0.0f);
     float t = 1.0f, hu, hv;
-    if (valid) {
-        const float4 o4 = p.sh_o[idx], d4 = p.sh_d[idx];
-        O = mk3(o4.x, o4.y, o4.z);
-        D = mk3(d4.x, d4.y, d4.z);
-        t = d4.w - 0.0001f;
-        if (t > 3.0e38f) t = 3.0e38f;
-    }
+    if (valid) load_shadow_ray(p, idx, O, D, t);
     int32_t hi = -1, ht = -1;
     bool occluded;
     const SceneView sv = scene_view(sc);
     traverse_packet<true, COUNT, FAR>(sv, sc.tlas_wide, sc.tlas_wide_stride, sc.blas_wide, sc.blas_wide_stride, valid, O, D, 0.001f, t, hu, hv, hi, ht, occluded, tc);
-    if (valid && !occluded) {
-        const float4 e = p.sh_e[idx];
-        const uint32_t slot = fbits(e.w);
-        float4 a = p.acc[slot]; // single writer per pixel per pass, as ray_shadow.comp:268
-        a.x += e.x; a.y += e.y; a.z += e.z; a.w += 0.0f;
-        p.acc[slot] = a;
-    }
+    if (valid && !occluded) add_contribution(p, idx);
     flush_counters<COUNT>(sc.counters, tc, 2);
 }
 
@@ -640,53 +613,26 @@ struct ShadowStream {
         const uint32_t i = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
         if (i >= end) return false;
         idx = base + i;
-        const float4 o4 = p.sh_o[idx], d4 = p.sh_d[idx];
-        O = mk3(o4.x, o4.y, o4.z);
-        D = mk3(d4.x, d4.y, d4.z);
-        t = d4.w - 0.0001f;
-        if (t > 3.0e38f) t = 3.0e38f;
+        load_shadow_ray(p, idx, O, D, t);
         return true;
     }
     RFW_DI void advance(const uint64_t idle) { next += (uint32_t)__popcll(idle); }
     RFW_DI void commit(const bool occluded, float, float, float, int32_t, int32_t)
     {
-        if (occluded) return;
-        const float4 e = p.sh_e[idx];
-        const uint32_t slot = fbits(e.w);
-        float4 a = p.acc[slot]; // single writer per pixel per pass, whichever lane traces the ray
-        a.x += e.x; a.y += e.y; a.z += e.z; a.w += 0.0f;
-        p.acc[slot] = a;
+        if (!occluded) add_contribution(p, idx);
     }
 };
 // One instantiation per visiting order (FAR: hit children by decreasing exit distance): a kernel that holds both traversals spills ~50 scalar
 // registers into vector lanes.  Each launch walks the buckets of its own order only.
-RFW_DI bool bucket_far_first(const CameraParams& cam, const uint32_t bucket)
-{
-    return bucket == (uint32_t)kShadowBuckets - 1u ? !(cam.flags & kFlagNearFirstDirectional) : (cam.flags & kFlagFarFirstPositional) != 0u;
-}
 template <bool COUNT, bool FAR>
 __global__ __launch_bounds__(kTraceBlock, kStreamWavesAny) void k_shadow_stream(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
 {
     __shared__ uint32_t s_stack[kTraceLdsRowsAny * kTraceBlock];
     const uint32_t run = cam.stream_run * kTraceBlock;
-    uint32_t block = xcd_run(blockIdx.x, 64u / cam.stream_run);
-    uint32_t bucket = 0, count = 0;
-    {
-        bool found = false;
-        for (int kk = 0; kk < kShadowBuckets; kk++) {
-            const int k = kShadowBuckets - 1 - kk;
-            if (bucket_far_first(cam, (uint32_t)k) != FAR) continue;
-            const uint32_t c = sc.counters->shadow[bounce][k];
-            const uint32_t nb = (c + run - 1u) / run;
-            if (!found) {
-                if (block < nb) { found = true; bucket = (uint32_t)k; count = c; }
-                else block -= nb;
-            }
-        }
-        if (!found) return;
-    }
+    const ShadowBucket b = find_shadow_bucket(sc, bounce, run, xcd_run(blockIdx.x, 64u / cam.stream_run), [&](const uint32_t k) { return bucket_far_first(cam, k) != FAR; });
+    if (!b.found) return;
     TravCounters tc{0, 0, 0};
-    ShadowStream st{p, bucket * p.capacity, block * run, min(count, (block + 1u) * run), 0u};
+    ShadowStream st{p, b.bucket * p.capacity, b.block * run, min(b.count, (b.block + 1u) * run), 0u};
     const SceneView sv = scene_view(sc);
     traverse_stream<true, COUNT, FAR>(sv, st, cam.stream_refill & 0xffu, cam.stream_refill >> 8, s_stack, threadIdx.x, blockIdx.x * kTraceBlock, tc);
     flush_counters<COUNT>(sc.counters, tc, 2);
@@ -1007,39 +953,49 @@ __device__ inline uint32_t srgb_encode(const float* s_t, float x)
         if (x >= s_t[lo + bit - 1]) lo += bit;
     return lo;
 }
+// the workgroup (256 threads) stages the step table in LDS; then the B, G, R, A bytes of a linear colour, in memory order (the surface is opaque)
+RFW_DI void stage_steps(float* s_t, const SrgbSteps& steps)
+{
+    s_t[threadIdx.x] = steps.t[threadIdx.x];
+    __syncthreads();
+}
+RFW_DI uint32_t encode_bgra8(const float* s_t, const float r, const float g, const float b)
+{
+    return srgb_encode(s_t, b) | (srgb_encode(s_t, g) << 8) | (srgb_encode(s_t, r) << 16) | 0xff000000u;
+}
 template <bool LINEAR>
 __global__ __launch_bounds__(256) void k_pack_bgra8(const float4* __restrict__ acc_slab, uint32_t* __restrict__ out, const uint64_t n, const uint32_t samples,
                                                    const SrgbSteps steps)
 {
     __shared__ float s_t[256];
-    s_t[threadIdx.x] = steps.t[threadIdx.x];
-    __syncthreads();
+    stage_steps(s_t, steps);
     const float s = (float)(int)samples;
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
         const float4 a = acc_slab[i];
-        const float r = finalise<LINEAR>(a.x, s), g = finalise<LINEAR>(a.y, s), b = finalise<LINEAR>(a.z, s);
-        out[i] = srgb_encode(s_t, b) | (srgb_encode(s_t, g) << 8) | (srgb_encode(s_t, r) << 16) | 0xff000000u;
+        out[i] = encode_bgra8(s_t, finalise<LINEAR>(a.x, s), finalise<LINEAR>(a.y, s), finalise<LINEAR>(a.z, s));
     }
 }
-// all-gathered finished slabs [world][frame][slab_elems] -> the frame, de-tiled (halves -> the float frame; bytes -> the presented frame)
+// De-tiling: pixel (px, py) of frame blockIdx.z of the batch -> the element of the all-gathered slabs [rank][frame][slab_elems] that holds it
+RFW_DI uint64_t gathered_element(const CameraParams& cam, const uint32_t px, const uint32_t py, const uint64_t slab_elems)
+{
+    uint32_t owner;
+    const uint32_t slot = pixel_to_slab(cam, px, py, owner);
+    const uint32_t f = blockIdx.z;
+    return ((uint64_t)owner * cam.batch + f) * slab_elems + slot;
+}
+// all-gathered finished slabs -> the frame, de-tiled (halves -> the float frame; bytes -> the presented frame)
 __global__ void k_assemble_f16(const CameraParams cam, const _Float16* __restrict__ gathered, const uint64_t slab_elems, float4* __restrict__ frame)
 {
     const uint32_t px = blockIdx.x * blockDim.x + threadIdx.x, py = blockIdx.y * blockDim.y + threadIdx.y;
     if (px >= cam.width || py >= cam.height) return;
-    uint32_t owner;
-    const uint32_t slot = pixel_to_slab(cam, px, py, owner);
-    const uint32_t f = blockIdx.z;
-    const _Float16* g = gathered + 3 * (((uint64_t)owner * cam.batch + f) * slab_elems + slot);
-    frame[(size_t)f * cam.width * cam.height + px + py * cam.width] = make_float4((float)g[0], (float)g[1], (float)g[2], 0.0f);
+    const _Float16* g = gathered + 3 * gathered_element(cam, px, py, slab_elems);
+    frame[(size_t)blockIdx.z * cam.width * cam.height + px + py * cam.width] = make_float4((float)g[0], (float)g[1], (float)g[2], 0.0f);
 }
 __global__ void k_assemble_bgra8(const CameraParams cam, const uint32_t* __restrict__ gathered, const uint64_t slab_elems, uint32_t* __restrict__ presented)
 {
     const uint32_t px = blockIdx.x * blockDim.x + threadIdx.x, py = blockIdx.y * blockDim.y + threadIdx.y;
     if (px >= cam.width || py >= cam.height) return;
-    uint32_t owner;
-    const uint32_t slot = pixel_to_slab(cam, px, py, owner);
-    const uint32_t f = blockIdx.z;
-    presented[(size_t)f * cam.width * cam.height + px + py * cam.width] = gathered[((uint64_t)owner * cam.batch + f) * slab_elems + slot];
+    presented[(size_t)blockIdx.z * cam.width * cam.height + px + py * cam.width] = gathered[gathered_element(cam, px, py, slab_elems)];
 }
 // rfw_hip_render_samples: the k sample slabs of one image -> slab 0, added in sample order (the same left-to-right sum per pixel whatever
 // the launch geometry: deterministic; it differs from k sequential render() calls only in where the partial sums are rounded)
@@ -1060,12 +1016,10 @@ __global__ __launch_bounds__(256) void k_sum_batch(float4* __restrict__ acc, con
 __global__ __launch_bounds__(256) void k_present(const float4* __restrict__ frame, uint32_t* __restrict__ bgra, const uint64_t n, const SrgbSteps steps)
 {
     __shared__ float s_t[256];
-    s_t[threadIdx.x] = steps.t[threadIdx.x];
-    __syncthreads();
-    auto enc = [&](float x) -> uint32_t { return srgb_encode(s_t, x); };
+    stage_steps(s_t, steps);
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
         const float4 c = frame[i];
-        bgra[i] = enc(c.z) | (enc(c.y) << 8) | (enc(c.x) << 16) | 0xff000000u; // B, G, R, A in memory order; the surface is opaque
+        bgra[i] = encode_bgra8(s_t, c.x, c.y, c.z);
     }
 }
 // all-gathered slabs [world][slab_elems] -> full frame.  RGB: the gathered buffer holds 3 floats per element (k_pack_rgb), else the
@@ -1079,18 +1033,15 @@ __global__ void k_assemble(const CameraParams cam, const void* __restrict__ gath
 {
     const uint32_t px = blockIdx.x * blockDim.x + threadIdx.x, py = blockIdx.y * blockDim.y + threadIdx.y;
     if (px >= cam.width || py >= cam.height) return;
-    uint32_t owner;
-    const uint32_t slot = pixel_to_slab(cam, px, py, owner);
-    const uint32_t f = blockIdx.z; // frame of a batch; gathered = [rank][frame][slot]
-    const uint64_t e = ((uint64_t)owner * cam.batch + f) * slab_elems + slot;
+    const uint64_t from = gathered_element(cam, px, py, slab_elems);
     float4 a;
     if (RGB) {
-        const float* g = static_cast<const float*>(gathered_v) + 3 * e;
+        const float* g = static_cast<const float*>(gathered_v) + 3 * from;
         a = make_float4(g[0], g[1], g[2], 0.0f);
     } else {
-        a = static_cast<const float4*>(gathered_v)[e];
+        a = static_cast<const float4*>(gathered_v)[from];
     }
-    frame += (size_t)f * cam.width * cam.height;
+    frame += (size_t)blockIdx.z * cam.width * cam.height;
     if (ACC) {
         frame[px + py * cam.width] = a;
     } else {
@@ -1100,6 +1051,11 @@ __global__ void k_assemble(const CameraParams cam, const void* __restrict__ gath
 }
 
 // ---------------------------------------------------------------- ray queries (TIntersector::intersect / occludes)
+RFW_DI void load_query_ray(const float* __restrict__ origins, const float* __restrict__ directions, const uint64_t idx, f3& O, f3& D)
+{
+    O = mk3(origins[3 * idx], origins[3 * idx + 1], origins[3 * idx + 2]);
+    D = mk3(directions[3 * idx], directions[3 * idx + 1], directions[3 * idx + 2]);
+}
 template <bool DEPTH>
 __global__ __launch_bounds__(kTraceBlock) void k_query_closest(const SceneDev sc, const float* __restrict__ origins, const float* __restrict__ directions,
                                                                 const float t_min, const float t_max, const uint64_t n, rfw_hip_hit* __restrict__ hits,
@@ -1108,8 +1064,8 @@ __global__ __launch_bounds__(kTraceBlock) void k_query_closest(const SceneDev sc
     __shared__ uint32_t s_stack[kTraceLdsRows * kTraceBlock];
     const uint64_t idx = (uint64_t)blockIdx.x * kTraceBlock + threadIdx.x;
     if (idx >= n) return;
-    const f3 O = mk3(origins[3 * idx], origins[3 * idx + 1], origins[3 * idx + 2]);
-    const f3 D = mk3(directions[3 * idx], directions[3 * idx + 1], directions[3 * idx + 2]);
+    f3 O, D;
+    load_query_ray(origins, directions, idx, O, D);
     // The search interval ends at a FINITE distance.  With t = +inf a degenerate ray (zero direction components: 1 / d = inf) gives child
     // boxes an entry distance of +inf that still passes `entry <= t`; such children tie with the +inf keys of the empty slots in the
     // ordering network, an empty slot's reference (kInvalidRef) can be taken for a child, and it decodes as a leaf far outside the
@@ -1117,13 +1073,12 @@ __global__ __launch_bounds__(kTraceBlock) void k_query_closest(const SceneDev sc
     float t = t_max > 3.0e38f ? 3.0e38f : t_max, hu = 0.0f, hv = 0.0f; // below FLT_MAX, the key the ordering network gives to children that are not hit
     int32_t hi = -1, ht = -1;
     TravCounters tc{0, 0, 0};
-    const SceneView sv = scene_view(sc);
-    traverse<false, DEPTH>(sv, O, D, t_min, t, hu, hv, hi, ht, s_stack, threadIdx.x, (uint32_t)((idx - threadIdx.x) % sc.spill_stride), tc);
+    traverse<false, DEPTH>(scene_view(sc), O, D, t_min, t, hu, hv, hi, ht, s_stack, threadIdx.x, (uint32_t)((idx - threadIdx.x) % sc.spill_stride), tc);
     if (hi < 0) t = t_max;
     rfw_hip_hit h;
     if (hi >= 0) { // storage order -> the boundary's triangle numbering (identical after a full build)
-        const MeshRecord r = sc.meshes[sc.instances[hi].mesh];
-        ht = (int32_t)((uint32_t)ht - r.tri_base + r.tri_logical);
+        const MeshRecord m = sc.meshes[sc.instances[hi].mesh];
+        ht = (int32_t)((uint32_t)ht - m.tri_base + m.tri_logical);
     }
     h.inst = hi; h.tri = ht; h.t = t; h.u = hu; h.v = hv;
     hits[idx] = h;
@@ -1137,14 +1092,13 @@ __global__ __launch_bounds__(kTraceBlock) void k_query_any(const SceneDev sc, co
     __shared__ uint32_t s_stack[kTraceLdsRowsAny * kTraceBlock];
     const uint64_t idx = (uint64_t)blockIdx.x * kTraceBlock + threadIdx.x;
     if (idx >= n) return;
-    const f3 O = mk3(origins[3 * idx], origins[3 * idx + 1], origins[3 * idx + 2]);
-    const f3 D = mk3(directions[3 * idx], directions[3 * idx + 1], directions[3 * idx + 2]);
+    f3 O, D;
+    load_query_ray(origins, directions, idx, O, D);
     float t = t_max[idx], hu, hv;
     if (t > 3.0e38f) t = 3.0e38f; // see k_query_closest: the interval ends at a finite distance (a NaN t_max stays NaN: nothing is hit)
     int32_t hi = -1, ht = -1;
     TravCounters tc{0, 0, 0};
-    const SceneView sv = scene_view(sc);
-    const bool occ = traverse<true, DEPTH>(sv, O, D, t_min, t, hu, hv, hi, ht, s_stack, threadIdx.x, (uint32_t)((idx - threadIdx.x) % sc.spill_stride), tc);
+    const bool occ = traverse<true, DEPTH>(scene_view(sc), O, D, t_min, t, hu, hv, hi, ht, s_stack, threadIdx.x, (uint32_t)((idx - threadIdx.x) % sc.spill_stride), tc);
     occluded[idx] = occ ? 1 : 0;
     if (DEPTH) depth[idx] = tc.nodes; // 4-wide nodes visited until the first occluder / the end of the traversal
 }
@@ -1158,6 +1112,13 @@ __global__ void k_quantize_nodes(const Node4* __restrict__ in, Node4Q* __restric
     if (i < n && (!live || i < *live)) out[i] = quantize_node(in[i]);
 }
 // one thread per (node, octant copy): the 1 KB of copies per node is the larger part of the traffic
+// (the packet form may be absent where no packet kernel can run: follow_copies; OCTQ_MAY_BE_ABSENT: so may the quantised form, k_tlas_finish)
+template <bool OCTQ_MAY_BE_ABSENT = false>
+RFW_DI void write_octant_copies(const Node4Q& q, const uint32_t i, const uint32_t oct, PacketNode* __restrict__ wide, Node4Q* __restrict__ octq, const uint32_t stride)
+{
+    if (wide) wide[(size_t)oct * stride + i] = make_packet_node(q, oct);
+    if (!OCTQ_MAY_BE_ABSENT || octq) octq[(size_t)oct * stride + i] = make_octant_node(q, oct);
+}
 __global__ void k_expand_nodes(const Node4Q* __restrict__ in, PacketNode* __restrict__ wide, Node4Q* __restrict__ octq, const uint32_t wide_stride, const uint32_t n,
                                const uint32_t* __restrict__ live)
 {
@@ -1165,8 +1126,7 @@ __global__ void k_expand_nodes(const Node4Q* __restrict__ in, PacketNode* __rest
     const uint32_t i = g >> 3, oct = g & 7u;
     if (i < n && (!live || i < *live)) {
         const Node4Q q = in[i];
-        if (wide) wide[(size_t)oct * wide_stride + i] = make_packet_node(q, oct); // (absent where no packet kernel can run: follow_copies)
-        octq[(size_t)oct * wide_stride + i] = make_octant_node(q, oct);
+        write_octant_copies(q, i, oct, wide, octq, wide_stride);
     }
 }
 RFW_DI bool slot_is_live(const MeshRecord* __restrict__ recs, const uint32_t* __restrict__ counts, const uint32_t n_recs, const uint32_t slot)
@@ -1191,8 +1151,7 @@ __global__ void k_expand_regions(const Node4Q* __restrict__ in, PacketNode* __re
     const uint32_t i = g >> 3, oct = g & 7u;
     if (i < n && slot_is_live(recs, counts, n_recs, i)) {
         const Node4Q q = in[i];
-        if (wide) wide[(size_t)oct * wide_stride + i] = make_packet_node(q, oct); // (absent where no packet kernel can run: follow_copies)
-        octq[(size_t)oct * wide_stride + i] = make_octant_node(q, oct);
+        write_octant_copies(q, i, oct, wide, octq, wide_stride);
     }
 }
 
@@ -1211,8 +1170,7 @@ __global__ __launch_bounds__(256) void k_tlas_finish(const Node4* __restrict__ r
         if (i < n_nodes_max && i < *live) {
             const Node4Q q = quantize_node(raw[i]);
             if (oct == 0u) out[i] = q;
-            if (wide) wide[(size_t)oct * wide_stride + i] = make_packet_node(q, oct);
-            if (octq) octq[(size_t)oct * wide_stride + i] = make_octant_node(q, oct);
+            write_octant_copies<true>(q, i, oct, wide, octq, wide_stride);
         }
     } else {
         const uint32_t i = (blockIdx.x - expand_blocks) * 256u + threadIdx.x;
@@ -1222,6 +1180,13 @@ __global__ __launch_bounds__(256) void k_tlas_finish(const Node4* __restrict__ r
 
 // ---------------------------------------------------------------- launch wrappers
 static inline uint32_t ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+static inline dim3 xcd_grid(const uint32_t blocks) { return dim3((blocks + 511u) & ~511u); } // padded for xcd_block / xcd_run
+// a run-time flag as a template argument: f(std::true_type) or f(std::false_type), for a generic lambda that names the kernel with `flag.value`
+template <class F> static inline void with_flag(const bool flag, const F& f)
+{
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
 static SrgbSteps make_steps(const float* steps255)
 {
     SrgbSteps st;
@@ -1246,97 +1211,64 @@ void launch_tlas_finish(hipStream_t s, const Node4* raw, Node4Q* out, const Octa
 }
 void launch_primary(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, bool count)
 {
-    const dim3 grid((ceil_div(p.capacity, kTraceBlock) + 511u) & ~511u), block(kTraceBlock);
-    if ((cam.flags & kFlagPacketPrimary) && sc.tlas_wide && sc.blas_wide) {
-        if (count) hipLaunchKernelGGL(k_primary_packet<true>, grid, block, 0, s, cam, sc, p);
-        else hipLaunchKernelGGL(k_primary_packet<false>, grid, block, 0, s, cam, sc, p);
-        return;
-    }
-    if (count) hipLaunchKernelGGL(k_primary<true>, grid, block, 0, s, cam, sc, p);
-    else hipLaunchKernelGGL(k_primary<false>, grid, block, 0, s, cam, sc, p);
+    const dim3 grid = xcd_grid(ceil_div(p.capacity, kTraceBlock)), block(kTraceBlock);
+    with_flag(count, [&](auto c) {
+        if ((cam.flags & kFlagPacketPrimary) && sc.tlas_wide && sc.blas_wide) hipLaunchKernelGGL(k_primary_packet<c.value>, grid, block, 0, s, cam, sc, p);
+        else hipLaunchKernelGGL(k_primary<c.value>, grid, block, 0, s, cam, sc, p);
+    });
 }
 void launch_primary_batch(hipStream_t s, const CameraParams& cam, const BatchViews& views, const SceneDev& sc, const PathDev& p, bool count)
 {
-    const dim3 grid((ceil_div(p.capacity, kTraceBlock) + 511u) & ~511u), block(kTraceBlock);
-    if ((cam.flags & kFlagPacketPrimary) && sc.tlas_wide && sc.blas_wide) {
-        if (count) hipLaunchKernelGGL(k_primary_batch_packet<true>, grid, block, 0, s, cam, views, sc, p);
-        else hipLaunchKernelGGL(k_primary_batch_packet<false>, grid, block, 0, s, cam, views, sc, p);
-        return;
-    }
-    if (count) hipLaunchKernelGGL(k_primary_batch<true>, grid, block, 0, s, cam, views, sc, p);
-    else hipLaunchKernelGGL(k_primary_batch<false>, grid, block, 0, s, cam, views, sc, p);
+    const dim3 grid = xcd_grid(ceil_div(p.capacity, kTraceBlock)), block(kTraceBlock);
+    with_flag(count, [&](auto c) {
+        if ((cam.flags & kFlagPacketPrimary) && sc.tlas_wide && sc.blas_wide) hipLaunchKernelGGL(k_primary_batch_packet<c.value>, grid, block, 0, s, cam, views, sc, p);
+        else hipLaunchKernelGGL(k_primary_batch<c.value>, grid, block, 0, s, cam, views, sc, p);
+    });
 }
 void launch_extend(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, uint32_t bounce, bool count, const uint32_t* order)
 {
     const dim3 block(kTraceBlock);
-    if (cam.stream_run) {
-        const dim3 grid((ceil_div(p.capacity, kTraceBlock * cam.stream_run) + 511u) & ~511u);
-        if (count) hipLaunchKernelGGL(k_extend_stream<true>, grid, block, 0, s, cam, sc, p, bounce, order);
-        else hipLaunchKernelGGL(k_extend_stream<false>, grid, block, 0, s, cam, sc, p, bounce, order);
-        return;
-    }
-    const dim3 grid((ceil_div(p.capacity, kTraceBlock) + 511u) & ~511u);
-    if (count) hipLaunchKernelGGL(k_extend<true>, grid, block, 0, s, cam, sc, p, bounce, order);
-    else hipLaunchKernelGGL(k_extend<false>, grid, block, 0, s, cam, sc, p, bounce, order);
+    with_flag(count, [&](auto c) {
+        if (cam.stream_run) hipLaunchKernelGGL(k_extend_stream<c.value>, xcd_grid(ceil_div(p.capacity, kTraceBlock * cam.stream_run)), block, 0, s, cam, sc, p, bounce, order);
+        else hipLaunchKernelGGL(k_extend<c.value>, xcd_grid(ceil_div(p.capacity, kTraceBlock)), block, 0, s, cam, sc, p, bounce, order);
+    });
 }
 void launch_shade(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, uint32_t bounce)
 {
     const bool small = (cam.flags & kFlagShadeSmallGroups) != 0u; // (do_render: several frame slots and one frame per call, or option "shade_group")
-    if (cam.batch > 1) {
-        if (small) hipLaunchKernelGGL((k_shade<true, 256>), dim3(ceil_div(p.capacity, 256)), dim3(256), 0, s, cam, sc, p, bounce);
-        else hipLaunchKernelGGL((k_shade<true, 512>), dim3(ceil_div(p.capacity, 512)), dim3(512), 0, s, cam, sc, p, bounce);
-    } else {
-        if (small) hipLaunchKernelGGL((k_shade<false, 256>), dim3(ceil_div(p.capacity, 256)), dim3(256), 0, s, cam, sc, p, bounce);
-        else hipLaunchKernelGGL((k_shade<false, 512>), dim3(ceil_div(p.capacity, 512)), dim3(512), 0, s, cam, sc, p, bounce);
-    }
+    with_flag(cam.batch > 1, [&](auto batch) {
+        if (small) hipLaunchKernelGGL((k_shade<batch.value, 256>), dim3(ceil_div(p.capacity, 256)), dim3(256), 0, s, cam, sc, p, bounce);
+        else hipLaunchKernelGGL((k_shade<batch.value, 512>), dim3(ceil_div(p.capacity, 512)), dim3(512), 0, s, cam, sc, p, bounce);
+    });
 }
 void launch_shadow(hipStream_t s, const CameraParams& cam_in, const SceneDev& sc, const PathDev& p, uint32_t bounce, bool count)
 {
     CameraParams cam = cam_in;
+    const bool packets_possible = bounce == 0 && sc.tlas_wide && sc.blas_wide && cam.batch <= 1;
     // (k_shadow leaves the far-to-near buckets to the packet launch below only when that launch happens)
-    if (!(bounce == 0 && sc.tlas_wide && sc.blas_wide && cam.batch <= 1) || (cam.flags & kFlagPacketShadow)) cam.flags &= ~kFlagPacketShadowFar;
-    if (bounce == 0 && (cam.flags & kFlagPacketShadow) && sc.tlas_wide && sc.blas_wide && cam.batch <= 1) {
-        // worst case: every path pushed a shadow ray, every bucket padded to whole wavefronts; one launch per visiting order
-        const uint32_t blocks_ = (p.capacity + kTraceBlock - 1) / kTraceBlock + kShadowBuckets;
-        const dim3 grid_(((blocks_ + 511u) / 512u) * 512u), block_(kTraceBlock);
-        if (count) {
-            hipLaunchKernelGGL((k_shadow_packet<true, true>), grid_, block_, 0, s, cam, sc, p, bounce);
-            hipLaunchKernelGGL((k_shadow_packet<true, false>), grid_, block_, 0, s, cam, sc, p, bounce);
-        } else {
-            hipLaunchKernelGGL((k_shadow_packet<false, true>), grid_, block_, 0, s, cam, sc, p, bounce);
-            hipLaunchKernelGGL((k_shadow_packet<false, false>), grid_, block_, 0, s, cam, sc, p, bounce);
+    if (!packets_possible || (cam.flags & kFlagPacketShadow)) cam.flags &= ~kFlagPacketShadowFar;
+    // worst case: every path pushed a shadow ray, every bucket padded to whole wavefronts
+    const dim3 grid = xcd_grid(ceil_div(p.capacity, kTraceBlock) + kShadowBuckets), block(kTraceBlock);
+    with_flag(count, [&](auto c) {
+        if (packets_possible && (cam.flags & kFlagPacketShadow)) { // one launch per visiting order
+            hipLaunchKernelGGL((k_shadow_packet<c.value, true>), grid, block, 0, s, cam, sc, p, bounce);
+            hipLaunchKernelGGL((k_shadow_packet<c.value, false>), grid, block, 0, s, cam, sc, p, bounce);
+            return;
         }
-        return;
-    }
-    if (cam.flags & kFlagPacketShadowFar) {
         // packets for the buckets traced far to near only (the directional lights: parallel rays from neighbouring pixels); k_shadow below skips them
-        const uint32_t blocks_ = (p.capacity + kTraceBlock - 1) / kTraceBlock + kShadowBuckets;
-        const dim3 grid_(((blocks_ + 511u) / 512u) * 512u), block_(kTraceBlock);
-        if (count) hipLaunchKernelGGL((k_shadow_packet<true, true>), grid_, block_, 0, s, cam, sc, p, bounce);
-        else hipLaunchKernelGGL((k_shadow_packet<false, true>), grid_, block_, 0, s, cam, sc, p, bounce);
-    }
-    const dim3 block(kTraceBlock);
-    // streaming pays where a wavefront's rays differ in length and direction: the shadow rays of the bounces.  The camera paths' own shadow rays
-    // (bounce 0) start on neighbouring pixels towards one light and stay one ray per lane (measured: -16 % when they stream too with the nested
-    // loops of rounds 3-4; break-even, 8012-8080 against 8059-8115 Mrays/s, with the flat ones of round 5)
-    if (cam.stream_run && bounce >= 1u) { // (a batch needs nothing special here: the queue entry carries the accumulator slot)
-        const dim3 grid((ceil_div(p.capacity, kTraceBlock * cam.stream_run) + kShadowBuckets + 511u) & ~511u);
-        // the two orders' launches follow each other on the stream (no rays of the other kind: the blocks return at once)
-        if (count) {
-            hipLaunchKernelGGL((k_shadow_stream<true, true>), grid, block, 0, s, cam, sc, p, bounce);
-            hipLaunchKernelGGL((k_shadow_stream<true, false>), grid, block, 0, s, cam, sc, p, bounce);
-        } else {
-            hipLaunchKernelGGL((k_shadow_stream<false, true>), grid, block, 0, s, cam, sc, p, bounce);
-            hipLaunchKernelGGL((k_shadow_stream<false, false>), grid, block, 0, s, cam, sc, p, bounce);
+        if (cam.flags & kFlagPacketShadowFar) hipLaunchKernelGGL((k_shadow_packet<c.value, true>), grid, block, 0, s, cam, sc, p, bounce);
+        // streaming pays where a wavefront's rays differ in length and direction: the shadow rays of the bounces.  The camera paths' own shadow rays
+        // (bounce 0) start on neighbouring pixels towards one light and stay one ray per lane (measured: -16 % when they stream too with the nested
+        // loops of rounds 3-4; break-even, 8012-8080 against 8059-8115 Mrays/s, with the flat ones of round 5)
+        if (cam.stream_run && bounce >= 1u) { // (a batch needs nothing special here: the queue entry carries the accumulator slot)
+            const dim3 stream_grid = xcd_grid(ceil_div(p.capacity, kTraceBlock * cam.stream_run) + kShadowBuckets);
+            // the two orders' launches follow each other on the stream (no rays of the other kind: the blocks return at once)
+            hipLaunchKernelGGL((k_shadow_stream<c.value, true>), stream_grid, block, 0, s, cam, sc, p, bounce);
+            hipLaunchKernelGGL((k_shadow_stream<c.value, false>), stream_grid, block, 0, s, cam, sc, p, bounce);
+            return;
         }
-        return;
-    }
-    const dim3 grid((ceil_div(p.capacity, kTraceBlock) + kShadowBuckets + 511u) & ~511u);
-    if (cam.batch > 1) {
-        if (count) hipLaunchKernelGGL((k_shadow<true, true>), grid, block, 0, s, cam, sc, p, bounce);
-        else hipLaunchKernelGGL((k_shadow<false, true>), grid, block, 0, s, cam, sc, p, bounce);
-    } else if (count) hipLaunchKernelGGL((k_shadow<true, false>), grid, block, 0, s, cam, sc, p, bounce);
-    else hipLaunchKernelGGL((k_shadow<false, false>), grid, block, 0, s, cam, sc, p, bounce);
+        with_flag(cam.batch > 1, [&](auto batch) { hipLaunchKernelGGL((k_shadow<c.value, batch.value>), grid, block, 0, s, cam, sc, p, bounce); });
+    });
 }
 // bandwidth probe: 16 B per lane per access; every workgroup owns chunks of 4 x 256 elements, 4 loads in flight per lane before the first
 // store, non-temporal on both sides (a copy streams: nothing is read again).  tools/probes/mem_probe.hip measured the variants on MI355X:
@@ -1452,13 +1384,10 @@ void launch_assemble(hipStream_t s, const CameraParams& cam, const void* gathere
                      uint32_t samples, bool linear)
 {
     const dim3 block(16, 4), grid(ceil_div(cam.width, 16), ceil_div(cam.height, 4), cam.batch > 1 ? cam.batch : 1u);
-    if (linear && !accumulator) {
-        if (rgb) hipLaunchKernelGGL((k_assemble<true, false, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
-        else hipLaunchKernelGGL((k_assemble<false, false, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
-    } else if (rgb && accumulator) hipLaunchKernelGGL((k_assemble<true, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
-    else if (rgb) hipLaunchKernelGGL((k_assemble<true, false>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
-    else if (accumulator) hipLaunchKernelGGL((k_assemble<false, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
-    else hipLaunchKernelGGL((k_assemble<false, false>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples);
+    with_flag(rgb, [&](auto rgb_) {
+        if (accumulator) hipLaunchKernelGGL((k_assemble<rgb_.value, true>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples); // (finalised neither way)
+        else with_flag(linear, [&](auto lin) { hipLaunchKernelGGL((k_assemble<rgb_.value, false, lin.value>), grid, block, 0, s, cam, gathered, slab_elems, frame, samples); });
+    });
 }
 // `narrow`: the destination is host memory written over the PCIe link: a few workgroups saturate the link, and more would only hold
 // wave slots the trace kernels of the other frames in flight want
@@ -1475,10 +1404,10 @@ void launch_pack_finished(hipStream_t s, const float4* acc_slab, void* out, uint
 {
     if (!n) return;
     const dim3 g16((unsigned)ceil_div(n, 256)), g8((unsigned)std::min<uint64_t>(ceil_div(n, 256), 8192));
-    if (format == 1 && linear) hipLaunchKernelGGL(k_pack_f16<true>, g16, dim3(256), 0, s, acc_slab, (_Float16*)out, n, samples);
-    else if (format == 1) hipLaunchKernelGGL(k_pack_f16<false>, g16, dim3(256), 0, s, acc_slab, (_Float16*)out, n, samples);
-    else if (linear) hipLaunchKernelGGL(k_pack_bgra8<true>, g8, dim3(256), 0, s, acc_slab, (uint32_t*)out, n, samples, make_steps(steps255));
-    else hipLaunchKernelGGL(k_pack_bgra8<false>, g8, dim3(256), 0, s, acc_slab, (uint32_t*)out, n, samples, make_steps(steps255));
+    with_flag(linear, [&](auto lin) {
+        if (format == 1) hipLaunchKernelGGL(k_pack_f16<lin.value>, g16, dim3(256), 0, s, acc_slab, (_Float16*)out, n, samples);
+        else hipLaunchKernelGGL(k_pack_bgra8<lin.value>, g8, dim3(256), 0, s, acc_slab, (uint32_t*)out, n, samples, make_steps(steps255));
+    });
 }
 void launch_assemble_finished(hipStream_t s, const CameraParams& cam, const void* gathered, uint64_t slab_elems, uint32_t format, float4* frame, uint32_t* presented)
 {
@@ -1576,15 +1505,14 @@ void launch_query_closest(hipStream_t s, const SceneDev& sc, const float* origin
 {
     if (n == 0) return;
     const dim3 grid(ceil_div(n, kTraceBlock)), block(kTraceBlock);
-    if (depth) hipLaunchKernelGGL(k_query_closest<true>, grid, block, 0, s, sc, origins, directions, t_min, t_max, n, hits, depth);
-    else hipLaunchKernelGGL(k_query_closest<false>, grid, block, 0, s, sc, origins, directions, t_min, t_max, n, hits, depth);
+    with_flag(depth != nullptr, [&](auto d) { hipLaunchKernelGGL(k_query_closest<d.value>, grid, block, 0, s, sc, origins, directions, t_min, t_max, n, hits, depth); });
 }
 void launch_query_any(hipStream_t s, const SceneDev& sc, const float* origins, const float* directions, float t_min, const float* t_max, uint64_t n,
                       uint8_t* occluded, uint32_t* depth)
 {
     if (n == 0) return;
-    if (depth) hipLaunchKernelGGL(k_query_any<true>, dim3(ceil_div(n, kTraceBlock)), dim3(kTraceBlock), 0, s, sc, origins, directions, t_min, t_max, n, occluded, depth);
-    else hipLaunchKernelGGL(k_query_any<false>, dim3(ceil_div(n, kTraceBlock)), dim3(kTraceBlock), 0, s, sc, origins, directions, t_min, t_max, n, occluded, depth);
+    const dim3 grid(ceil_div(n, kTraceBlock)), block(kTraceBlock);
+    with_flag(depth != nullptr, [&](auto d) { hipLaunchKernelGGL(k_query_any<d.value>, grid, block, 0, s, sc, origins, directions, t_min, t_max, n, occluded, depth); });
 }
 
 // ---------------------------------------------------------------- render modes 1-6 (rfw_hip_render's `mode`)
