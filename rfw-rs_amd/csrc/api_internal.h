@@ -400,18 +400,17 @@ struct Instance {
     uint64_t n_instances = 0, n_valid_instances = 0, n_tris = 0, n_blas_nodes = 0, n_tlas_nodes = 0; // (n_tris: stored primitives, duplicates included)
     uint64_t n_tris_logical = 0; // the caller's triangles
     float ms_blas_build = 0, ms_tlas_build = 0, ms_stage_wait = 0;
-    float ms_blas_upload = 0, ms_blas_kernels = 0; // the last full device build, by events
+    float ms_blas_upload = 0, ms_blas_kernels = 0; // the last device build, by events
     uint64_t blas_upload_bytes = 0, blas_kernel_bytes = 0;
     // small meshes are built side by side: one worker thread per auxiliary stream, each with scratch of its own (build_meshes)
     struct BuildLane { hipStream_t s = nullptr; hipEvent_t done = nullptr; DevBuf<char> ws; DevBuf<DevBox> boxes; };
     static constexpr int kBuildLanes = 8;
     BuildLane lanes[kBuildLanes];
     hipEvent_t ev_build[3] = {nullptr, nullptr, nullptr};
-    // full device build: the 48-B heads go up on `stream`, the 176-B records behind them on `records_stream` while the trees are built
+    // heads-first upload (upload_heads_first): the 48-B heads go up on `stream`, the 176-B records behind them on `records_stream` while the trees are built
     DevBuf<TriHead> d_heads;
     hipStream_t records_stream = nullptr;
     hipEvent_t ev_heads = nullptr, ev_records = nullptr;
-    bool build_from_heads = false; // (inside build_blas_device_full only)
     bool records_pending = false;  // an upload from a registered host copy was queued and nobody has waited for ev_records yet
     bool records_timed = false;    // the last build recorded ev_records (scene stats: upload time = until the records have arrived)
     bool build_events_pending = false; // recorded, not read yet (rfw_hip_get_scene_stats reads them: no synchronisation for them in synchronize())

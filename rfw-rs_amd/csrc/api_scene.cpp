@@ -193,21 +193,27 @@ uint64_t build_pass_bytes(uint64_t n)
     return n * (208u + 116u * levels + 40u + 228u) + (n / 4u) * 320u;
 }
 
+// a record of the mega-buffers that a build (re)builds, with the host mesh it comes from
+struct RecordSource { uint32_t q; const MeshHost* mesh; };
+// How the trees of one build are made: decided by build_blas_device_full / _incremental, passed down to build_meshes, build_mesh_device and the lanes
+struct BuildPlan {
+    bool from_heads;   // the records are still on their way (upload_heads_first): boxes from d_heads; the packets, which need the records, are left to the caller behind ev_records
+    bool quantise_now; // each record's nodes are quantised behind its tree (incremental build); a full build quantises all regions in one launch at its end
+};
+
 // Spatial splits at build time.  upload_split_pieces: the box overrides of the records about to be built go up as one table (used only while
 // those records are built); patch_boxes: behind k_triangle_boxes, the references of split triangles get the boxes of their parts (`boxes` =
 // the record's first box); resolve_duplicates: behind k_make_packets, the packets of duplicate records take their original's id.
-int upload_split_pieces(Instance* I, const std::vector<uint32_t>& qs)
+int upload_split_pieces(Instance* I, const std::vector<RecordSource>& build)
 {
     I->record_piece_off.assign(I->mesh_records.size(), 0u);
     I->record_piece_n.assign(I->mesh_records.size(), 0u);
     std::vector<SplitPiece> all;
-    for (const auto& kv : I->mesh_index) {
-        if (std::find(qs.begin(), qs.end(), kv.second) == qs.end()) continue;
-        const auto mit = I->meshes.find(kv.first);
-        if (mit == I->meshes.end() || mit->second.pieces.empty()) continue;
-        I->record_piece_off[kv.second] = (uint32_t)all.size();
-        I->record_piece_n[kv.second] = (uint32_t)mit->second.pieces.size();
-        all.insert(all.end(), mit->second.pieces.begin(), mit->second.pieces.end());
+    for (const RecordSource& b : build) {
+        if (b.mesh->pieces.empty()) continue;
+        I->record_piece_off[b.q] = (uint32_t)all.size();
+        I->record_piece_n[b.q] = (uint32_t)b.mesh->pieces.size();
+        all.insert(all.end(), b.mesh->pieces.begin(), b.mesh->pieces.end());
     }
     if (all.empty()) return RFW_HIP_OK;
     HIP_TRY(I, I->d_split_pieces.ensure(all.size()));
@@ -225,10 +231,10 @@ inline void resolve_duplicates(Instance* I, hipStream_t s, uint32_t q)
         launch_resolve_duplicates(s, I->d_packets.ptr + r.tri_base, r.tri_count, r.tri_base, I->record_tri_orig[q], I->d_triangles.ptr + r.tri_base);
 }
 // boxes of a record's primitives (from the heads while a build runs ahead of the records), references of split triangles patched
-inline void record_boxes(Instance* I, hipStream_t s, uint32_t q, DevBox* out)
+inline void record_boxes(Instance* I, hipStream_t s, uint32_t q, bool from_heads, DevBox* out)
 {
     const MeshRecord& r = I->mesh_records[q];
-    if (I->build_from_heads) launch_triangle_boxes(s, I->d_heads.ptr + r.tri_base, r.tri_count, out);
+    if (from_heads) launch_triangle_boxes(s, I->d_heads.ptr + r.tri_base, r.tri_count, out);
     else launch_triangle_boxes(s, I->d_triangles.ptr + r.tri_base, r.tri_count, out);
     patch_boxes(I, s, q, out);
 }
@@ -238,45 +244,51 @@ inline void record_packets(Instance* I, hipStream_t s, uint32_t q)
     launch_make_packets(s, I->d_triangles.ptr + r.tri_base, I->d_blas_order.ptr + r.tri_base, r.tri_count, r.tri_base, I->d_packets.ptr + r.tri_base);
     resolve_duplicates(I, s, q);
 }
+// behind a record's tree, where the plan says so: packets, quantised nodes (the region is sized for one node per primitive; nodes behind the tree's own are never referenced)
+inline void record_finish(Instance* I, hipStream_t s, uint32_t q, const BuildPlan& plan)
+{
+    const MeshRecord& r = I->mesh_records[q];
+    if (!plan.from_heads) record_packets(I, s, q);
+    if (plan.quantise_now)
+        launch_quantize_nodes(s, I->d_blas_raw.ptr + r.node_base, I->d_blas_nodes.ptr + r.node_base, copies_of(I->d_blas_wide, I->d_blas_oct), r.node_base, std::max(r.tri_count, 1u), I->d_mesh_node_counts.ptr + q);
+}
+
+// One tree over n boxes on stream s: binned SAH, and LBVH where the tree is deeper than the SAH builder's level budget above its LDS phase
+// (LBVH always terminates); LBVH alone where the instance does not build SAH on the device (`sah` false).
+int build_tree(Instance* I, hipStream_t s, bool sah, const DevBox* boxes, uint32_t n, DevBuf<char>& sah_ws, const DevBuf<char>& lbvh_ws, Node4* raw, uint32_t* order, uint32_t* count)
+{
+    if (sah) {
+        HIP_TRY(I, sah_ws.ensure(sah_workspace_bytes(n)));
+        const hipError_t se = sah_build(s, boxes, n, sah_ws.ptr, sah_ws.cap, raw, order, count, I->sah_max_leaf, I->sah_trav_cost);
+        if (se != hipErrorInvalidValue) { HIP_TRY(I, se); return RFW_HIP_OK; }
+    }
+    HIP_TRY(I, lbvh_build(s, boxes, n, lbvh_ws.ptr, lbvh_ws.cap, raw, order, count));
+    return RFW_HIP_OK;
+}
 
 // One static mesh on the device, into the region its record names: boxes -> BVH (binned SAH, or LBVH) -> leaf-ordered packets ->
-// quantised nodes.  The triangles are already in d_triangles.  `quantise_count` nodes of the region are quantised (the region is sized for
-// the worst case, one node per primitive; nodes behind the tree's own are never referenced).
-int build_mesh_device(Instance* I, uint32_t q, uint32_t quantise_count)
+// quantised nodes.  The triangles (or, with plan.from_heads, their heads) are already on the device.
+int build_mesh_device(Instance* I, uint32_t q, const BuildPlan& plan)
 {
     const MeshRecord& r = I->mesh_records[q];
     if (r.tri_count == 0) return RFW_HIP_OK;
-    record_boxes(I, I->stream, q, I->d_tri_boxes.ptr);
-    if (I->blas_sah_on_device) {
-        HIP_TRY(I, I->d_sah_ws.ensure(sah_workspace_bytes(r.tri_count)));
-        const hipError_t se = sah_build(I->stream, I->d_tri_boxes.ptr, r.tri_count, I->d_sah_ws.ptr, I->d_sah_ws.cap, I->d_blas_raw.ptr + r.node_base,
-                                        I->d_blas_order.ptr + r.tri_base, I->d_mesh_node_counts.ptr + q, I->sah_max_leaf, I->sah_trav_cost);
-        if (se == hipErrorInvalidValue) { // a tree deeper than the SAH builder's level budget above its LDS phase: LBVH always terminates
-            HIP_TRY(I, lbvh_build(I->stream, I->d_tri_boxes.ptr, r.tri_count, I->d_lbvh_ws.ptr, I->d_lbvh_ws.cap, I->d_blas_raw.ptr + r.node_base,
-                                  I->d_blas_order.ptr + r.tri_base, I->d_mesh_node_counts.ptr + q));
-        } else {
-            HIP_TRY(I, se);
-        }
-    } else {
-        HIP_TRY(I, lbvh_build(I->stream, I->d_tri_boxes.ptr, r.tri_count, I->d_lbvh_ws.ptr, I->d_lbvh_ws.cap, I->d_blas_raw.ptr + r.node_base,
-                              I->d_blas_order.ptr + r.tri_base, I->d_mesh_node_counts.ptr + q));
-    }
-    // (a full build makes the packets of all meshes at its end: they need the records, which are still on their way while the trees are built)
-    if (!I->build_from_heads) record_packets(I, I->stream, q);
-    launch_quantize_nodes(I->stream, I->d_blas_raw.ptr + r.node_base, I->d_blas_nodes.ptr + r.node_base, copies_of(I->d_blas_wide, I->d_blas_oct), r.node_base, quantise_count, I->d_mesh_node_counts.ptr + q);
-    return RFW_HIP_OK;
+    record_boxes(I, I->stream, q, plan.from_heads, I->d_tri_boxes.ptr);
+    const int rc = build_tree(I, I->stream, I->blas_sah_on_device, I->d_tri_boxes.ptr, r.tri_count, I->d_sah_ws, I->d_lbvh_ws, I->d_blas_raw.ptr + r.node_base,
+                              I->d_blas_order.ptr + r.tri_base, I->d_mesh_node_counts.ptr + q);
+    if (rc == RFW_HIP_OK) record_finish(I, I->stream, q, plan);
+    return rc;
 }
 
 // Several meshes: the large ones one after the other on the instance's stream (each fills the device by itself), the small ones side by
 // side — a 5120-triangle mesh is ~30 dependent launches of a few microseconds and one 16-byte read-back, i.e. all latency: kBuildLanes host
 // threads, each with a stream and scratch of its own, take them from one counter.  The lanes start behind what the instance's stream holds
 // (the triangle uploads) and the stream continues behind the lanes.  A builder failure falls back to the one-by-one path for that mesh.
-int build_meshes(Instance* I, const std::vector<uint32_t>& qs, bool incremental)
+int build_meshes(Instance* I, const std::vector<RecordSource>& build, const BuildPlan plan)
 {
     constexpr uint32_t kSmallMesh = 131072;
     std::vector<uint32_t> small, large;
-    for (const uint32_t q : qs) (I->blas_sah_on_device && I->mesh_records[q].tri_count && I->mesh_records[q].tri_count <= kSmallMesh ? small : large).push_back(q);
-    if (small.size() < 2) { large = qs; small.clear(); }
+    for (const RecordSource& b : build) (I->blas_sah_on_device && I->mesh_records[b.q].tri_count && I->mesh_records[b.q].tri_count <= kSmallMesh ? small : large).push_back(b.q);
+    if (small.size() < 2) { large.clear(); for (const RecordSource& b : build) large.push_back(b.q); small.clear(); }
     int rc = RFW_HIP_OK;
     const int n_lanes = (int)std::min<size_t>(Instance::kBuildLanes, small.size());
     std::vector<std::thread> workers;
@@ -296,25 +308,25 @@ int build_meshes(Instance* I, const std::vector<uint32_t>& qs, bool incremental)
             HIP_TRY(I, hipStreamWaitEvent(L.s, start, 0));
         }
         for (int k = 0; k < n_lanes; k++)
-            workers.emplace_back([I, k, &small, &next, &lane_err, &redo, incremental] {
+            workers.emplace_back([I, k, &small, &next, &lane_err, &redo, plan] {
                 Instance::BuildLane& L = I->lanes[k];
                 if (hipSetDevice(I->device) != hipSuccess) { lane_err[k] = hipErrorInvalidDevice; return; }
                 for (size_t i = next.fetch_add(1); i < small.size(); i = next.fetch_add(1)) {
                     const uint32_t q = small[i];
                     const MeshRecord& r = I->mesh_records[q];
-                    record_boxes(I, L.s, q, L.boxes.ptr);
+                    record_boxes(I, L.s, q, plan.from_heads, L.boxes.ptr);
                     const hipError_t e = sah_build(L.s, L.boxes.ptr, r.tri_count, L.ws.ptr, L.ws.cap, I->d_blas_raw.ptr + r.node_base, I->d_blas_order.ptr + r.tri_base,
                                                    I->d_mesh_node_counts.ptr + q, I->sah_max_leaf, I->sah_trav_cost);
-                    if (e == hipErrorInvalidValue) { redo[q] = 1; continue; } // deeper than the builder's level budget: LBVH, below
+                    // deeper than the builder's level budget: LBVH, below, on the instance's stream (the LBVH workspace is the instance's, not a lane's)
+                    if (e == hipErrorInvalidValue) { redo[q] = 1; continue; }
                     if (e != hipSuccess) { lane_err[k] = e; return; }
-                    if (!I->build_from_heads) record_packets(I, L.s, q);
-                    if (incremental) launch_quantize_nodes(L.s, I->d_blas_raw.ptr + r.node_base, I->d_blas_nodes.ptr + r.node_base, copies_of(I->d_blas_wide, I->d_blas_oct), r.node_base, std::max(r.tri_count, 1u), I->d_mesh_node_counts.ptr + q);
+                    record_finish(I, L.s, q, plan);
                 }
                 (void)hipEventRecord(L.done, L.s);
             });
     }
     for (const uint32_t q : large) // meanwhile, on the instance's own stream
-        if (rc == RFW_HIP_OK) rc = build_mesh_device(I, q, incremental ? std::max(I->mesh_records[q].tri_count, 1u) : 0u);
+        if (rc == RFW_HIP_OK) rc = build_mesh_device(I, q, plan);
     for (auto& t : workers) t.join();
     for (int k = 0; k < n_lanes; k++) {
         if (lane_err[k] != hipSuccess && rc == RFW_HIP_OK) rc = fail(I, RFW_HIP_E_DEVICE, std::string("build lane: ") + hipGetErrorString(lane_err[k]));
@@ -322,7 +334,7 @@ int build_meshes(Instance* I, const std::vector<uint32_t>& qs, bool incremental)
     }
     if (rc != RFW_HIP_OK) return rc;
     for (const uint32_t q : small)
-        if (redo[q] && (rc = build_mesh_device(I, q, incremental ? std::max(I->mesh_records[q].tri_count, 1u) : 0u))) return rc;
+        if (redo[q] && (rc = build_mesh_device(I, q, plan))) return rc;
     return RFW_HIP_OK;
 }
 
@@ -343,216 +355,157 @@ void assign_logical_ids(Instance* I)
     I->n_tris_logical = logical;
 }
 
-// BLAS for every mesh on the device: lay the mega-buffers out afresh, upload all triangles, build every mesh
-int build_blas_device_full(Instance* I)
+// Heads first: the builders read 48 of a record's 176 B, so those go up on the instance's stream and the trees are built while the records
+// follow on a stream of their own (registered host memory: both copies are asynchronous).  Only the packets and the renderer need the
+// records; the caller makes the stream wait for ev_records before the packets are made.  (C4, 185 MB: upload 3.5 ms + kernels 4.5 ms one after
+// the other before.)  The heads lie at their records' positions: d_heads gets `heads_cap` triangle slots.
+int upload_heads_first(Instance* I, const std::vector<RecordSource>& send, size_t heads_cap)
 {
-    const bool kTrace = env_switches().build_trace; // (stderr: where a full build's host time goes)
-    const auto t_start = std::chrono::steady_clock::now();
-    auto trace = [&](const char* what) {
-        if (kTrace) fprintf(stderr, "[build] %-28s %7.3f ms\n", what, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_start).count());
-    };
+    HIP_TRY(I, I->d_heads.ensure(heads_cap));
+    if (!I->records_stream) HIP_TRY(I, hipStreamCreateWithFlags(&I->records_stream, hipStreamNonBlocking));
+    if (!I->ev_heads) HIP_TRY(I, hipEventCreate(&I->ev_heads));
+    if (!I->ev_records) HIP_TRY(I, hipEventCreate(&I->ev_records));
+    // meshes too small to be registered go through the pinned ring, and FIRST: a staged copy may have to wait for a ring block, i.e. for
+    // an earlier copy on its stream — behind a 127 MB record copy that would hold the host back from queuing the build
+    for (int pass = 0; pass < 2; pass++)
+        for (const RecordSource& b : send) {
+            const MeshRecord& r = I->mesh_records[b.q];
+            if (!r.tri_count || (int)b.mesh->pinned != pass) continue;
+            const size_t bytes = (size_t)r.tri_count * sizeof(TriHead);
+            if (b.mesh->pinned) HIP_TRY(I, hipMemcpyAsync(I->d_heads.ptr + r.tri_base, b.mesh->heads.data(), bytes, hipMemcpyHostToDevice, I->stream));
+            else HIP_TRY(I, I->pins.upload(I->d_heads.ptr + r.tri_base, b.mesh->heads.data(), bytes, I->stream));
+        }
+    HIP_TRY(I, hipEventRecord(I->ev_heads, I->stream));
+    HIP_TRY(I, hipStreamWaitEvent(I->records_stream, I->ev_heads, 0)); // (behind the heads on the link, and behind everything the instance's stream waited for)
+    for (int pass = 0; pass < 2; pass++)
+        for (const RecordSource& b : send) {
+            const MeshRecord& r = I->mesh_records[b.q];
+            if (!r.tri_count || (int)b.mesh->pinned != pass) continue;
+            const size_t bytes = (size_t)r.tri_count * sizeof(rfw_rt_triangle);
+            if (b.mesh->pinned) HIP_TRY(I, hipMemcpyAsync(I->d_triangles.ptr + r.tri_base, b.mesh->tris.data(), bytes, hipMemcpyHostToDevice, I->records_stream));
+            else HIP_TRY(I, I->pins.upload(I->d_triangles.ptr + r.tri_base, b.mesh->tris.data(), bytes, I->records_stream));
+        }
+    HIP_TRY(I, hipEventRecord(I->ev_records, I->records_stream));
+    // from here on a copy may be reading the registered host arrays: should anything after this fail, the next set_3d_mesh / unload waits for
+    // ev_records before it touches them (a full build clears this behind its final synchronisation; an incremental build synchronises nothing)
+    I->records_pending = true;
+    I->records_timed = true;
+    I->heads_first_builds++;
+    return RFW_HIP_OK;
+}
+
+// build scratch (~350 B per triangle) above `limit` bytes is not kept between scene changes
+void trim_build_scratch(Instance* I, size_t limit)
+{
+    if (I->d_sah_ws.cap > limit) I->d_sah_ws.release();
+    for (auto& L : I->lanes)
+        if (L.ws.cap > limit) { L.ws.release(); L.boxes.release(); }
+}
+
+struct BuildTrace { // RFW_BUILD_TRACE (stderr: where a full build's host time goes)
+    const bool on = env_switches().build_trace;
+    const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    void operator()(const char* what) const { if (on) fprintf(stderr, "[build] %-28s %7.3f ms\n", what, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_start).count()); }
+};
+struct FullLayout { // what a full build lays out: the static meshes (record k = the k-th mesh), then the skinned copies
+    std::vector<RecordSource> statics;
+    uint32_t static_tris = 0, static_nodes = 0, tri_total = 0, node_total = 0, max_n = 0; // (max_n: triangles of the largest static mesh)
+};
+
+// Full build, step 1: one record per mesh, one region of the mega-buffers per record, the buffers themselves
+int layout_records(Instance* I, FullLayout& L)
+{
     I->mesh_records.clear();
     I->mesh_index.clear();
     I->record_tri_cap.clear();
     I->record_tri_orig.clear();
-    uint32_t tri_total = 0, node_total = 0;
     for (auto& kv : I->meshes) {
         MeshRecord r;
         std::memset(&r, 0, sizeof(r));
-        r.tri_base = tri_total;
+        r.tri_base = L.tri_total;
         r.tri_count = (uint32_t)kv.second.n_refs; // stored primitives: the caller's triangles + the duplicates of split ones
         I->record_tri_orig.push_back((uint32_t)kv.second.n_orig);
-        r.node_base = node_total;
+        r.node_base = L.node_total;
         r.node_count = std::max<uint32_t>(r.tri_count, 1u); // worst case (one primitive per leaf => at most n - 1 wide nodes)
-        tri_total += r.tri_count;
-        node_total += r.node_count;
+        L.tri_total += r.tri_count;
+        L.node_total += r.node_count;
+        L.max_n = std::max(L.max_n, r.tri_count);
+        L.statics.push_back(RecordSource{(uint32_t)I->mesh_records.size(), &kv.second});
         I->mesh_index[kv.first] = (uint32_t)I->mesh_records.size();
         I->mesh_records.push_back(r);
         I->record_tri_cap.push_back(r.tri_count);
         kv.second.dirty = false;
     }
-    const uint32_t static_nodes = node_total, static_tris = tri_total;
-    const size_t n_static = I->mesh_records.size();
+    L.static_nodes = L.node_total;
+    L.static_tris = L.tri_total;
     I->raw_node_origin = 0;
-    int rc;
-    if ((rc = layout_derived(I, tri_total, node_total))) return rc;
+    if (const int rc = layout_derived(I, L.tri_total, L.node_total)) return rc;
     assign_logical_ids(I);
-    HIP_TRY(I, I->d_triangles.ensure(tri_total));
-    HIP_TRY(I, I->d_packets.ensure(tri_total));
-    HIP_TRY(I, I->d_blas_nodes.ensure(node_total));
-    HIP_TRY(I, follow_copies(I->d_blas_wide, I->d_blas_oct, I->d_blas_nodes, 0, I->stream, blas_wide_wanted(I, tri_total)));
-    HIP_TRY(I, I->d_blas_raw.ensure(node_total));
-    HIP_TRY(I, I->d_blas_order.ensure(tri_total));
-    for (auto& ev : I->ev_build)
-        if (!ev) HIP_TRY(I, hipEventCreate(&ev));
-    HIP_TRY(I, hipEventRecord(I->ev_build[0], I->stream));
-    {
-        std::vector<uint32_t> all_static(n_static);
-        for (size_t q = 0; q < n_static; q++) all_static[q] = (uint32_t)q;
-        if ((rc = upload_split_pieces(I, all_static))) return rc;
-    }
-    // Heads first: the builders read 48 of a record's 176 B, so those go up on the instance's stream and the trees are built while the records
-    // follow on a stream of their own (registered host memory: both copies are asynchronous).  Only the packets and the renderer need the
-    // records; the stream waits for them before the packets are made.  (C4, 185 MB: upload 3.5 ms + kernels 4.5 ms one after the other before.)
-    uint32_t max_n = 0;
-    size_t k = 0;
-    bool any_pinned = false; // (a scene of small meshes only: nothing to overlap; an unregistered mesh is staged by the runtime on either stream)
-    for (auto& kv : I->meshes) any_pinned = any_pinned || kv.second.pinned;
-    I->build_from_heads = any_pinned && static_tris > 0;
-    I->records_timed = I->build_from_heads;
-    if (I->build_from_heads) I->heads_first_builds++;
-    if (I->build_from_heads) {
-        HIP_TRY(I, I->d_heads.ensure(static_tris));
-        if (!I->records_stream) HIP_TRY(I, hipStreamCreateWithFlags(&I->records_stream, hipStreamNonBlocking));
-        if (!I->ev_heads) HIP_TRY(I, hipEventCreate(&I->ev_heads));
-        if (!I->ev_records) HIP_TRY(I, hipEventCreate(&I->ev_records));
-        // meshes too small to be registered go through the pinned ring, and FIRST: a staged copy may have to wait for a ring block, i.e. for
-        // an earlier copy on its stream — behind a 127 MB record copy that would hold the host back from queuing the build
-        for (int pass = 0; pass < 2; pass++) {
-            k = 0;
-            for (auto& kv : I->meshes) {
-                const MeshRecord& r = I->mesh_records[k++];
-                max_n = std::max(max_n, r.tri_count);
-                if (!r.tri_count || (int)kv.second.pinned != pass) continue;
-                const size_t bytes = (size_t)r.tri_count * sizeof(TriHead);
-                if (kv.second.pinned) HIP_TRY(I, hipMemcpyAsync(I->d_heads.ptr + r.tri_base, kv.second.heads.data(), bytes, hipMemcpyHostToDevice, I->stream));
-                else HIP_TRY(I, I->pins.upload(I->d_heads.ptr + r.tri_base, kv.second.heads.data(), bytes, I->stream));
-            }
-        }
-        HIP_TRY(I, hipEventRecord(I->ev_heads, I->stream));
-        HIP_TRY(I, hipStreamWaitEvent(I->records_stream, I->ev_heads, 0)); // (behind the heads on the link, and behind everything the instance's stream waited for)
-        for (int pass = 0; pass < 2; pass++) {
-            k = 0;
-            for (auto& kv : I->meshes) {
-                const MeshRecord& r = I->mesh_records[k++];
-                if (!r.tri_count || (int)kv.second.pinned != pass) continue;
-                const size_t bytes = (size_t)r.tri_count * sizeof(rfw_rt_triangle);
-                if (kv.second.pinned) HIP_TRY(I, hipMemcpyAsync(I->d_triangles.ptr + r.tri_base, kv.second.tris.data(), bytes, hipMemcpyHostToDevice, I->records_stream));
-                else HIP_TRY(I, I->pins.upload(I->d_triangles.ptr + r.tri_base, kv.second.tris.data(), bytes, I->records_stream));
-            }
-        }
-        HIP_TRY(I, hipEventRecord(I->ev_records, I->records_stream));
-        // from here on a copy may be reading the registered host arrays: should anything below fail, the next set_3d_mesh / unload waits for
-        // ev_records before it touches them (cleared behind the final synchronisation of a build that went through)
-        I->records_pending = true;
-        trace("uploads queued");
-    } else {
-        for (auto& kv : I->meshes) {
-            const MeshRecord& r = I->mesh_records[k++];
-            max_n = std::max(max_n, r.tri_count);
-            if (r.tri_count)
-                HIP_TRY(I, hipMemcpyAsync(I->d_triangles.ptr + r.tri_base, kv.second.tris.data(), (size_t)r.tri_count * sizeof(rfw_rt_triangle),
-                                          hipMemcpyHostToDevice, I->stream));
-        }
-    }
-    HIP_TRY(I, I->d_tri_boxes.ensure(std::max(max_n, I->max_derived_tris)));
-    if ((rc = ensure_lbvh_ws(I, max_n))) return rc;
+    HIP_TRY(I, I->d_triangles.ensure(L.tri_total));
+    HIP_TRY(I, I->d_packets.ensure(L.tri_total));
+    HIP_TRY(I, I->d_blas_nodes.ensure(L.node_total));
+    HIP_TRY(I, follow_copies(I->d_blas_wide, I->d_blas_oct, I->d_blas_nodes, 0, I->stream, blas_wide_wanted(I, L.tri_total)));
+    HIP_TRY(I, I->d_blas_raw.ensure(L.node_total));
+    HIP_TRY(I, I->d_blas_order.ensure(L.tri_total));
+    return RFW_HIP_OK;
+}
+
+// Full build, step 3: the trees of all static meshes, and their packets (with `from_heads` behind ev_records: the records are still on their way)
+int build_static_trees(Instance* I, const FullLayout& L, bool from_heads, const BuildTrace& trace)
+{
+    const size_t n_static = L.statics.size();
+    HIP_TRY(I, I->d_tri_boxes.ensure(std::max(L.max_n, I->max_derived_tris)));
+    if (const int rc = ensure_lbvh_ws(I, L.max_n)) return rc;
     HIP_TRY(I, I->d_mesh_node_counts.ensure(std::max<size_t>(n_static, 1)));
     HIP_TRY(I, hipMemsetAsync(I->d_mesh_node_counts.ptr, 0, std::max<size_t>(n_static, 1) * 4, I->stream)); // (an empty mesh is not built: its count stays 0)
     HIP_TRY(I, hipEventRecord(I->ev_build[1], I->stream));
-    uint64_t kernel_bytes = 0;
-    {
-        std::vector<uint32_t> all(n_static);
-        for (size_t q = 0; q < n_static; q++) { all[q] = (uint32_t)q; kernel_bytes += build_pass_bytes(I->mesh_records[q].tri_count); }
-        // several meshes: ONE build for all of them (sah_build_forest: the meshes lie one after the other in the buffers of a full build, every
-        // mesh is a root of the same level-by-level pass) — ~45 launches for the scene instead of ~30 per mesh
-        bool forest_done = false;
-        // (measured: two meshes of 720 k + 330 k triangles 5.4 ms together, 4.4 ms one after the other; 65 meshes 5.5 ms against 10.4 on lanes, 38 one by one)
-        constexpr size_t forest_min = 4;
-        if (I->blas_sah_on_device && n_static >= forest_min && static_tris > 0 && !env_switches().no_forest) {
-            std::vector<ForestTree> trees(n_static);
-            for (size_t q = 0; q < n_static; q++) trees[q] = ForestTree{I->mesh_records[q].tri_base, I->mesh_records[q].tri_count, I->mesh_records[q].node_base, 0u};
-            HIP_TRY(I, I->d_forest.ensure(n_static));
-            HIP_TRY(I, I->pins.upload(I->d_forest.ptr, trees.data(), n_static * sizeof(ForestTree), I->stream));
-            HIP_TRY(I, I->d_tri_boxes.ensure(std::max(static_tris, I->max_derived_tris)));
-            HIP_TRY(I, I->d_sah_ws.ensure(sah_forest_workspace_bytes(static_tris, (uint32_t)n_static)));
-            if (I->build_from_heads) launch_triangle_boxes(I->stream, I->d_heads.ptr, static_tris, I->d_tri_boxes.ptr);
-            else launch_triangle_boxes(I->stream, I->d_triangles.ptr, static_tris, I->d_tri_boxes.ptr);
-            for (size_t q = 0; q < n_static; q++) patch_boxes(I, I->stream, (uint32_t)q, I->d_tri_boxes.ptr + I->mesh_records[q].tri_base);
-            const hipError_t fe = sah_build_forest(I->stream, I->d_tri_boxes.ptr, static_tris, I->d_forest.ptr, (uint32_t)n_static, max_n, I->d_sah_ws.ptr, I->d_sah_ws.cap,
-                                                   I->d_blas_raw.ptr, I->d_blas_order.ptr, I->d_mesh_node_counts.ptr, I->sah_max_leaf, I->sah_trav_cost);
-            if (fe == hipSuccess) {
-                if (I->build_from_heads) HIP_TRY(I, hipStreamWaitEvent(I->stream, I->ev_records, 0));
-                launch_make_packets(I->stream, I->d_triangles.ptr, I->d_blas_order.ptr, static_tris, 0u, I->d_packets.ptr); // global positions: one launch
-                for (size_t q = 0; q < n_static; q++) resolve_duplicates(I, I->stream, (uint32_t)q);
-                launch_forest_relative_order(I->stream, I->d_blas_order.ptr, static_tris, I->d_forest.ptr, (uint32_t)n_static);
-                forest_done = true;
-            } else if (fe != hipErrorInvalidValue) {
-                HIP_TRY(I, fe);
-            } // else: some tree is deeper than the builder's level budget: mesh by mesh, where LBVH can take over for that one
+    // several meshes: ONE build for all of them (sah_build_forest: the meshes lie one after the other in the buffers of a full build, every
+    // mesh is a root of the same level-by-level pass) — ~45 launches for the scene instead of ~30 per mesh
+    // (measured: two meshes of 720 k + 330 k triangles 5.4 ms together, 4.4 ms one after the other; 65 meshes 5.5 ms against 10.4 on lanes, 38 one by one)
+    constexpr size_t forest_min = 4;
+    if (I->blas_sah_on_device && n_static >= forest_min && L.static_tris > 0 && !env_switches().no_forest) {
+        std::vector<ForestTree> trees(n_static);
+        for (size_t q = 0; q < n_static; q++) trees[q] = ForestTree{I->mesh_records[q].tri_base, I->mesh_records[q].tri_count, I->mesh_records[q].node_base, 0u};
+        HIP_TRY(I, I->d_forest.ensure(n_static));
+        HIP_TRY(I, I->pins.upload(I->d_forest.ptr, trees.data(), n_static * sizeof(ForestTree), I->stream));
+        HIP_TRY(I, I->d_tri_boxes.ensure(std::max(L.static_tris, I->max_derived_tris)));
+        HIP_TRY(I, I->d_sah_ws.ensure(sah_forest_workspace_bytes(L.static_tris, (uint32_t)n_static)));
+        if (from_heads) launch_triangle_boxes(I->stream, I->d_heads.ptr, L.static_tris, I->d_tri_boxes.ptr);
+        else launch_triangle_boxes(I->stream, I->d_triangles.ptr, L.static_tris, I->d_tri_boxes.ptr);
+        for (size_t q = 0; q < n_static; q++) patch_boxes(I, I->stream, (uint32_t)q, I->d_tri_boxes.ptr + I->mesh_records[q].tri_base);
+        const hipError_t fe = sah_build_forest(I->stream, I->d_tri_boxes.ptr, L.static_tris, I->d_forest.ptr, (uint32_t)n_static, L.max_n, I->d_sah_ws.ptr, I->d_sah_ws.cap,
+                                               I->d_blas_raw.ptr, I->d_blas_order.ptr, I->d_mesh_node_counts.ptr, I->sah_max_leaf, I->sah_trav_cost);
+        if (fe == hipSuccess) {
+            if (from_heads) HIP_TRY(I, hipStreamWaitEvent(I->stream, I->ev_records, 0));
+            launch_make_packets(I->stream, I->d_triangles.ptr, I->d_blas_order.ptr, L.static_tris, 0u, I->d_packets.ptr); // global positions: one launch
+            for (size_t q = 0; q < n_static; q++) resolve_duplicates(I, I->stream, (uint32_t)q);
+            launch_forest_relative_order(I->stream, I->d_blas_order.ptr, L.static_tris, I->d_forest.ptr, (uint32_t)n_static);
+            return RFW_HIP_OK;
         }
-        if (!forest_done) {
-            rc = build_meshes(I, all, false);
-            trace("trees queued");
-            if (I->build_from_heads) { // the packets of every mesh, now that the records are (about to be) there
-                I->build_from_heads = false;
-                HIP_TRY(I, hipStreamWaitEvent(I->stream, I->ev_records, 0));
-                if (rc == RFW_HIP_OK)
-                    for (size_t q = 0; q < n_static; q++)
-                        if (I->mesh_records[q].tri_count) record_packets(I, I->stream, (uint32_t)q);
-            }
-            if (rc) return rc;
-        }
-        I->build_from_heads = false;
+        if (fe != hipErrorInvalidValue) HIP_TRY(I, fe);
+        // else: some tree is deeper than the builder's level budget: mesh by mesh, where LBVH can take over for that one
     }
-    if (env_switches().node_order && n_static) {
-        // EXPERIMENT (round 6): the builders number the 4-wide nodes in arrival order; renumber every static tree on the host —
-        // 1: depth-first (a node, then the subtree of its first child, ...), 2: treelets of up to 32 nodes (breadth-first inside a treelet,
-        // treelets depth-first) — and measure what the caches make of it beyond their reach (bench.py --workload atrium32m)
-        HIP_TRY(I, hipStreamSynchronize(I->stream));
-        std::vector<uint32_t> cnt(n_static, 0u);
-        HIP_TRY(I, hipMemcpy(cnt.data(), I->d_mesh_node_counts.ptr, n_static * 4, hipMemcpyDeviceToHost));
-        for (size_t q = 0; q < n_static; q++) {
-            const uint32_t n = cnt[q];
-            if (n < 2) continue;
-            Node4* dev = I->d_blas_raw.ptr + (I->mesh_records[q].node_base - I->raw_node_origin);
-            std::vector<Node4> in(n), out(n);
-            HIP_TRY(I, hipMemcpy(in.data(), dev, (size_t)n * sizeof(Node4), hipMemcpyDeviceToHost));
-            std::vector<uint32_t> order; // order[new] = old
-            order.reserve(n);
-            auto interior = [&](uint32_t c) { return c != kInvalidRef && !(c & kLeafBit); };
-            if (env_switches().node_order == 1) {
-                std::vector<uint32_t> stack{0u};
-                while (!stack.empty()) {
-                    const uint32_t v = stack.back(); stack.pop_back();
-                    order.push_back(v);
-                    for (int k = 3; k >= 0; k--) if (interior(in[v].child[k])) stack.push_back(in[v].child[k]);
-                }
-            } else {
-                std::vector<uint32_t> roots{0u}; // treelet roots, depth-first (a stack)
-                while (!roots.empty()) {
-                    const uint32_t r = roots.back(); roots.pop_back();
-                    std::vector<uint32_t> fifo{r};
-                    size_t head = 0;
-                    std::vector<uint32_t> spill;
-                    while (head < fifo.size()) {
-                        const uint32_t v = fifo[head++];
-                        order.push_back(v);
-                        for (int k = 0; k < 4; k++) {
-                            const uint32_t c = in[v].child[k];
-                            if (!interior(c)) continue;
-                            if (fifo.size() < 32) fifo.push_back(c); else spill.push_back(c);
-                        }
-                    }
-                    for (size_t k = spill.size(); k-- > 0;) roots.push_back(spill[k]);
-                }
-            }
-            if (order.size() != n) return fail(I, RFW_HIP_E_STATE, "RFW_NODE_ORDER: the tree does not reach every node of its region");
-            std::vector<uint32_t> where(n);
-            for (uint32_t k = 0; k < n; k++) where[order[k]] = k;
-            for (uint32_t k = 0; k < n; k++) {
-                out[k] = in[order[k]];
-                for (int c = 0; c < 4; c++) if (interior(out[k].child[c])) out[k].child[c] = where[out[k].child[c]];
-            }
-            HIP_TRY(I, hipMemcpy(dev, out.data(), (size_t)n * sizeof(Node4), hipMemcpyHostToDevice));
-        }
+    const int rc = build_meshes(I, L.statics, BuildPlan{from_heads, false});
+    trace("trees queued");
+    if (from_heads) { // the packets of every mesh, now that the records are (about to be) there
+        HIP_TRY(I, hipStreamWaitEvent(I->stream, I->ev_records, 0));
+        if (rc == RFW_HIP_OK)
+            for (size_t q = 0; q < n_static; q++)
+                if (I->mesh_records[q].tri_count) record_packets(I, I->stream, (uint32_t)q);
     }
-    if ((rc = upload(I, I->d_mesh_records, I->mesh_records.data(), I->mesh_records.size()))) return rc;
+    return rc;
+}
+
+// Full build, step 4: the records, all static regions quantised, the build waited for, what the statistics and the incremental path need
+int finish_full_build(Instance* I, const FullLayout& L, const BuildTrace& trace)
+{
+    const size_t n_static = L.statics.size();
+    if (const int rc = upload(I, I->d_mesh_records, I->mesh_records.data(), I->mesh_records.size())) return rc;
     // all static regions in one launch; the slots behind a tree's last node are skipped (the builders left the node counts on the device)
-    launch_quantize_regions(I->stream, I->d_blas_raw.ptr, I->d_blas_nodes.ptr, copies_of(I->d_blas_wide, I->d_blas_oct), static_nodes, I->d_mesh_records.ptr,
+    launch_quantize_regions(I->stream, I->d_blas_raw.ptr, I->d_blas_nodes.ptr, copies_of(I->d_blas_wide, I->d_blas_oct), L.static_nodes, I->d_mesh_records.ptr,
                             I->d_mesh_node_counts.ptr, (uint32_t)n_static);
     HIP_TRY(I, hipGetLastError());
-    I->n_tris = tri_total;
+    I->n_tris = L.tri_total;
     I->n_split_refs = 0;
     for (size_t q = 0; q < n_static; q++) I->n_split_refs += I->mesh_records[q].tri_count - I->record_tri_orig[q];
     HIP_TRY(I, hipEventRecord(I->ev_build[2], I->stream));
@@ -560,7 +513,7 @@ int build_blas_device_full(Instance* I)
     HIP_TRY(I, hipStreamSynchronize(I->stream));
     I->records_pending = false;
     trace("device done");
-    if (kTrace && I->records_timed) {
+    if (trace.on && I->records_timed) {
         float a = 0, b = 0, c = 0;
         (void)hipEventElapsedTime(&c, I->ev_build[0], I->ev_heads);
         fprintf(stderr, "[build] by events: heads arrived %.3f ms\n", c);
@@ -569,26 +522,61 @@ int build_blas_device_full(Instance* I)
         fprintf(stderr, "[build] by events: records arrived %.3f ms, build done %.3f ms after the start\n", a, b);
     }
     I->build_events_pending = true;
-    I->blas_upload_bytes = (uint64_t)static_tris * sizeof(rfw_rt_triangle);
-    I->blas_kernel_bytes = kernel_bytes;
+    I->blas_upload_bytes = (uint64_t)L.static_tris * sizeof(rfw_rt_triangle);
+    I->blas_kernel_bytes = 0;
+    for (size_t q = 0; q < n_static; q++) I->blas_kernel_bytes += build_pass_bytes(I->mesh_records[q].tri_count);
     // nodes actually in use (the regions are sized for the worst case, one node per primitive); skinned copies count at their worst case
     std::vector<uint32_t> counts(n_static, 0u);
     if (n_static) HIP_TRY(I, hipMemcpy(counts.data(), I->d_mesh_node_counts.ptr, n_static * 4, hipMemcpyDeviceToHost));
-    I->n_blas_nodes = node_total - static_nodes;
+    I->n_blas_nodes = L.node_total - L.static_nodes;
     for (uint32_t c : counts) I->n_blas_nodes += c;
     I->node_counts_stale = false;
     // ~350 B per triangle of build scratch: kept between scene changes up to 1 GB.  Not for the allocation's own cost: a hipFree / hipMalloc of
     // 0.4 GB between two builds made the NEXT build's record upload crawl beside its kernels (measured, C4: records arrived after 7.5 ms instead
     // of 4.4, every warm build 7.9 ms instead of 5.6 — tools/probes/h2d_overlap.cpp shows the copy itself overlaps kernels at full rate)
-    if (I->d_sah_ws.cap > (size_t(1) << 30)) I->d_sah_ws.release();
-    for (auto& L : I->lanes)
-        if (L.ws.cap > (size_t(1) << 30)) { L.ws.release(); L.boxes.release(); }
-    I->tri_end = static_tris;
-    I->node_end = static_nodes;
+    trim_build_scratch(I, size_t(1) << 30);
+    I->tri_end = L.static_tris;
+    I->node_end = L.static_nodes;
     I->hole_tris = 0;
     I->layout_valid = I->derived.empty(); // the incremental path does not move skinned copies around
     I->full_builds++;
     return RFW_HIP_OK;
+}
+
+// Full build, step 2: the triangles go up — heads first where some mesh is registered (a scene of small meshes only: nothing to overlap; an
+// unregistered mesh is staged by the runtime on either stream), else the records on the instance's stream.  ev_build[0] marks the start.
+int upload_static_meshes(Instance* I, const FullLayout& L, const BuildTrace& trace, bool& heads_first)
+{
+    for (auto& ev : I->ev_build)
+        if (!ev) HIP_TRY(I, hipEventCreate(&ev));
+    HIP_TRY(I, hipEventRecord(I->ev_build[0], I->stream));
+    if (const int rc = upload_split_pieces(I, L.statics)) return rc;
+    bool any_pinned = false;
+    for (const RecordSource& b : L.statics) any_pinned = any_pinned || b.mesh->pinned;
+    heads_first = any_pinned && L.static_tris > 0;
+    I->records_timed = false;
+    if (heads_first) {
+        if (const int rc = upload_heads_first(I, L.statics, L.static_tris)) return rc;
+        trace("uploads queued");
+    } else {
+        for (const RecordSource& b : L.statics)
+            if (const MeshRecord& r = I->mesh_records[b.q]; r.tri_count)
+                HIP_TRY(I, hipMemcpyAsync(I->d_triangles.ptr + r.tri_base, b.mesh->tris.data(), (size_t)r.tri_count * sizeof(rfw_rt_triangle), hipMemcpyHostToDevice, I->stream));
+    }
+    return RFW_HIP_OK;
+}
+
+// BLAS for every mesh on the device: lay the mega-buffers out afresh, upload all triangles, build every mesh
+int build_blas_device_full(Instance* I)
+{
+    const BuildTrace trace{};
+    FullLayout L;
+    bool heads_first = false;
+    int rc;
+    if ((rc = layout_records(I, L))) return rc;
+    if ((rc = upload_static_meshes(I, L, trace, heads_first))) return rc;
+    if ((rc = build_static_trees(I, L, heads_first, trace))) return rc;
+    return finish_full_build(I, L, trace);
 }
 
 // Only the meshes that changed (gpu-rt/src/lib.rs:1345-1383 rebuilds / refits `mesh.dirty` ones only): a changed mesh keeps its region of the
@@ -596,7 +584,6 @@ int build_blas_device_full(Instance* I)
 // Returns 1 when the layout has to be redone by a full build (too many holes), 0 on success, < 0 on error.
 int build_blas_device_incremental(Instance* I)
 {
-    I->build_from_heads = false;
     I->records_timed = false;
     // what went away
     for (auto it = I->mesh_index.begin(); it != I->mesh_index.end();) {
@@ -606,7 +593,7 @@ int build_blas_device_incremental(Instance* I)
             it = I->mesh_index.erase(it);
         } else ++it;
     }
-    std::vector<uint32_t> todo; // record indices to (re)build
+    std::vector<RecordSource> todo; // records to (re)build
     uint32_t max_n = 0;
     for (auto& kv : I->meshes) {
         MeshHost& m = kv.second;
@@ -639,7 +626,7 @@ int build_blas_device_incremental(Instance* I)
         I->mesh_records[q].tri_count = n;
         I->record_tri_orig[q] = (uint32_t)m.n_orig;
         I->mesh_records[q].node_count = std::max(I->record_tri_cap[q], 1u);
-        todo.push_back(q);
+        todo.push_back(RecordSource{q, &m});
         max_n = std::max(max_n, n);
         m.dirty = false;
     }
@@ -663,74 +650,42 @@ int build_blas_device_incremental(Instance* I)
         if (!ev) HIP_TRY(I, hipEventCreate(&ev));
     HIP_TRY(I, hipEventRecord(I->ev_build[0], I->stream));
     if ((rc = upload_split_pieces(I, todo))) return rc;
-    uint64_t upload_bytes = 0, kernel_bytes = 0;
+    I->blas_upload_bytes = I->blas_kernel_bytes = 0;
+    for (const RecordSource& b : todo) {
+        I->blas_upload_bytes += (uint64_t)I->mesh_records[b.q].tri_count * sizeof(rfw_rt_triangle);
+        I->blas_kernel_bytes += build_pass_bytes(I->mesh_records[b.q].tri_count);
+    }
     // ONE large registered mesh changed (a deforming mesh that is re-sent every frame): heads first, as in a full build — the tree is built
     // from the 48-B heads while the records follow on the second stream, the packets are made when they are there.  Nothing is synchronised
     // here: the next set_3d_mesh waits for ev_records before it overwrites the host copy the upload reads (records_pending).
-    bool heads_first = false;
-    if (todo.size() == 1 && I->mesh_records[todo[0]].tri_count * sizeof(rfw_rt_triangle) >= (size_t(1) << 20)) {
-        const uint32_t q = todo[0];
-        MeshHost* mh = nullptr;
-        for (auto& kv : I->mesh_index)
-            if (kv.second == q) mh = &I->meshes[kv.first];
-        if (mh && mh->pinned) {
-            const MeshRecord& r = I->mesh_records[q];
-            HIP_TRY(I, I->d_heads.ensure(I->tri_end));
-            if (!I->records_stream) HIP_TRY(I, hipStreamCreateWithFlags(&I->records_stream, hipStreamNonBlocking));
-            if (!I->ev_heads) HIP_TRY(I, hipEventCreate(&I->ev_heads));
-            if (!I->ev_records) HIP_TRY(I, hipEventCreate(&I->ev_records));
-            HIP_TRY(I, hipMemcpyAsync(I->d_heads.ptr + r.tri_base, mh->heads.data(), (size_t)r.tri_count * sizeof(TriHead), hipMemcpyHostToDevice, I->stream));
-            HIP_TRY(I, hipEventRecord(I->ev_heads, I->stream));
-            HIP_TRY(I, hipStreamWaitEvent(I->records_stream, I->ev_heads, 0));
-            HIP_TRY(I, hipMemcpyAsync(I->d_triangles.ptr + r.tri_base, mh->tris.data(), (size_t)r.tri_count * sizeof(rfw_rt_triangle), hipMemcpyHostToDevice, I->records_stream));
-            HIP_TRY(I, hipEventRecord(I->ev_records, I->records_stream));
-            I->records_pending = true;
-            I->records_timed = true;
-            I->heads_first_builds++;
-            upload_bytes += (uint64_t)r.tri_count * sizeof(rfw_rt_triangle);
-            heads_first = true;
-        }
-    }
-    for (const uint32_t q : todo) { // the changed meshes' triangles first (their regions are disjoint) ...
+    const bool heads_first = todo.size() == 1 && I->mesh_records[todo[0].q].tri_count * sizeof(rfw_rt_triangle) >= (size_t(1) << 20) && todo[0].mesh->pinned;
+    if (heads_first && (rc = upload_heads_first(I, todo, I->tri_end))) return rc;
+    for (const RecordSource& b : todo) { // the changed meshes' triangles first (their regions are disjoint) ...
         if (heads_first) break;
-        const MeshRecord& r = I->mesh_records[q];
-        const MeshHost* mh = nullptr;
-        for (auto& kv : I->mesh_index)
-            if (kv.second == q) mh = &I->meshes[kv.first];
-        if (r.tri_count && mh) {
-            upload_bytes += (uint64_t)r.tri_count * sizeof(rfw_rt_triangle);
-            // through the pinned ring when small (the host copy may be replaced by the next set_3d_mesh before a pageable copy has run)
-            if ((size_t)r.tri_count * sizeof(rfw_rt_triangle) <= (8u << 20))
-                HIP_TRY(I, I->pins.upload(I->d_triangles.ptr + r.tri_base, mh->tris.data(), (size_t)r.tri_count * sizeof(rfw_rt_triangle), I->stream));
-            else {
-                HIP_TRY(I, hipMemcpyAsync(I->d_triangles.ptr + r.tri_base, mh->tris.data(), (size_t)r.tri_count * sizeof(rfw_rt_triangle), hipMemcpyHostToDevice, I->stream));
-                HIP_TRY(I, hipStreamSynchronize(I->stream));
-            }
+        const MeshRecord& r = I->mesh_records[b.q];
+        const size_t bytes = (size_t)r.tri_count * sizeof(rfw_rt_triangle);
+        // through the pinned ring when small (the host copy may be replaced by the next set_3d_mesh before a pageable copy has run)
+        if (bytes <= (8u << 20)) HIP_TRY(I, I->pins.upload(I->d_triangles.ptr + r.tri_base, b.mesh->tris.data(), bytes, I->stream));
+        else {
+            HIP_TRY(I, hipMemcpyAsync(I->d_triangles.ptr + r.tri_base, b.mesh->tris.data(), bytes, hipMemcpyHostToDevice, I->stream));
+            HIP_TRY(I, hipStreamSynchronize(I->stream));
         }
     }
     HIP_TRY(I, hipEventRecord(I->ev_build[1], I->stream));
-    for (const uint32_t q : todo) kernel_bytes += build_pass_bytes(I->mesh_records[q].tri_count);
-    I->build_from_heads = heads_first;
-    rc = build_meshes(I, todo, true); // ... then their trees
-    I->build_from_heads = false;
-    if (rc) return rc;
+    if ((rc = build_meshes(I, todo, BuildPlan{heads_first, true}))) return rc; // ... then their trees
     if (heads_first) {
-        const MeshRecord& r = I->mesh_records[todo[0]];
         HIP_TRY(I, hipStreamWaitEvent(I->stream, I->ev_records, 0));
-        (void)r;
-        record_packets(I, I->stream, todo[0]);
+        record_packets(I, I->stream, todo[0].q);
     }
     HIP_TRY(I, hipEventRecord(I->ev_build[2], I->stream));
     I->build_events_pending = true;
-    I->blas_upload_bytes = upload_bytes;
-    I->blas_kernel_bytes = kernel_bytes;
     HIP_TRY(I, hipGetLastError());
     HIP_TRY(I, I->pins.upload(I->d_mesh_records.ptr, I->mesh_records.data(), I->mesh_records.size() * sizeof(MeshRecord), I->stream));
-    uint64_t live = 0;
-    for (auto& kv : I->mesh_index) live += I->mesh_records[kv.second].tri_count;
-    I->n_tris = live;
-    I->n_split_refs = 0;
-    for (auto& kv : I->mesh_index) I->n_split_refs += I->mesh_records[kv.second].tri_count - I->record_tri_orig[kv.second];
+    I->n_tris = I->n_split_refs = 0;
+    for (auto& kv : I->mesh_index) {
+        I->n_tris += I->mesh_records[kv.second].tri_count;
+        I->n_split_refs += I->mesh_records[kv.second].tri_count - I->record_tri_orig[kv.second];
+    }
     I->node_counts_stale = true;
     I->incremental_builds++;
     return RFW_HIP_OK;
@@ -746,9 +701,7 @@ int build_blas_device(Instance* I)
         const int rc = build_blas_device_incremental(I);
         // build scratch is not kept between scene changes when it is large (as after a full build: ~350 B per triangle); the scratch of small
         // edits stays — hipFree waits for the device, and an edit of one 5120-triangle mesh would pay its own build time on the host for it
-        if (I->d_sah_ws.cap > (64u << 20)) I->d_sah_ws.release();
-        for (auto& L : I->lanes)
-            if (L.ws.cap > (64u << 20)) { L.ws.release(); L.boxes.release(); }
+        trim_build_scratch(I, 64u << 20);
         if (rc < 0) { // an error part-way through: records, capacities and dirty flags may be half-updated — the next synchronize() starts over
             I->layout_valid = false;
             for (auto& kv : I->meshes) kv.second.dirty = true;
@@ -938,19 +891,12 @@ int build_instances(Instance* I, Instance* T)
             uint32_t quantise_count = r.node_count;
             if (!refit) {
                 launch_triangle_boxes(s, tris, r.tri_count, I->d_tri_boxes.ptr);
-                HIP_TRY(I, lbvh_build(s, I->d_tri_boxes.ptr, r.tri_count, T->d_lbvh_ws.ptr, T->d_lbvh_ws.cap, raw, order, nullptr));
+                if ((rc = build_tree(I, s, false, I->d_tri_boxes.ptr, r.tri_count, I->d_sah_ws, T->d_lbvh_ws, raw, order, nullptr))) return rc;
             } else if (!d.topology_built) {
-                // first pose of this (mesh, skin) pair: the tree, by binned SAH (blocking, once), and what a refit needs to climb it
+                // first pose of this (mesh, skin) pair: the tree, by binned SAH or LBVH as for static meshes (blocking, once), and what a refit needs to climb it
                 launch_triangle_boxes(s, tris, r.tri_count, I->d_tri_boxes.ptr);
-                HIP_TRY(I, I->d_sah_ws.ensure(sah_workspace_bytes(r.tri_count)));
                 HIP_TRY(I, T->d_node_count.ensure(1));
-                const hipError_t se = sah_build(s, I->d_tri_boxes.ptr, r.tri_count, I->d_sah_ws.ptr, I->d_sah_ws.cap, raw, order, T->d_node_count.ptr, I->sah_max_leaf,
-                                                I->sah_trav_cost);
-                if (se == hipErrorInvalidValue) { // deeper than the SAH builder's level budget: LBVH always terminates (as for static meshes)
-                    HIP_TRY(I, lbvh_build(s, I->d_tri_boxes.ptr, r.tri_count, T->d_lbvh_ws.ptr, T->d_lbvh_ws.cap, raw, order, T->d_node_count.ptr));
-                } else {
-                    HIP_TRY(I, se);
-                }
+                if ((rc = build_tree(I, s, true, I->d_tri_boxes.ptr, r.tri_count, I->d_sah_ws, T->d_lbvh_ws, raw, order, T->d_node_count.ptr))) return rc;
                 HIP_TRY(I, hipMemcpyAsync(&d.node_count, T->d_node_count.ptr, 4, hipMemcpyDeviceToHost, s));
                 HIP_TRY(I, hipStreamSynchronize(s));
                 if (d.node_count == 0 || d.node_count > r.node_count) return fail(I, RFW_HIP_E_STATE, "skinned BLAS: node count out of range");

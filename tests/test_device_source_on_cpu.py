@@ -49,3 +49,10 @@ def test_parity_tests_on_the_emulated_kernels(emulated_library):
                                            "closest_hit_bit_exact or any_hit_exact or edge_cases or radiance_matches_oracle or counts_and_queues or accumulation_reset or "
                                            "animated_instances_match_oracle or builders_give_identical_answers"])
     assert " passed" in out and "failed" not in out, out
+
+
+def test_device_build_paths_on_the_emulated_library(emulated_library):
+    """The host side of the device BLAS build (tests/test_gpu_api.py, at sizes the emulation can take): plain and heads-first uploads, forest and
+    lanes, the incremental build in place, appended, on the lanes and heads first — the build counters name the path, the oracle the result."""
+    out = run_gpu_tests(emulated_library, ["tests/test_gpu_api.py", "-k", "every_upload_and_tree_path_of_the_device_build"])
+    assert "1 passed" in out, out

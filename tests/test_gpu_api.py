@@ -676,6 +676,75 @@ def test_resent_meshes_upload_heads_first_and_give_the_same_image():
     be.close()
 
 
+def test_every_upload_and_tree_path_of_the_device_build_at_the_smallest_sizes(monkeypatch):
+    """The paths of the device BLAS build at the smallest sizes that still take them (a host copy is registered from 128 KB = 745 triangles on,
+    the incremental build goes heads first from 1 MiB = 5958 triangles on), so that the CPU-emulated library can run them too
+    (tests/test_device_source_on_cpu.py): plain and heads-first upload, the forest and the lanes with the packets made behind the records, the
+    incremental build in place, appended, on the lanes and heads first.  Which path a step took is read from the build counters [full,
+    incremental, heads first, registered meshes]; after every step ray queries and one frame equal the oracle's bit for bit."""
+    from oracle.bindings import Oracle
+    from rfw_rs_amd import HipBackend, Scene
+    w, h = 64, 36
+    rng = np.random.default_rng(3)
+    n = 2000
+    o = np.stack([rng.uniform(-14, 14, n), rng.uniform(0.2, 11.5, n), rng.uniform(-5.5, 5.5, n)], axis=1).astype(np.float32)
+    d = rng.normal(size=(n, 3)).astype(np.float32)
+    k = n // 2                                               # half of them aimed at the two rows of spheres, so that edits of single spheres are seen
+    d[:k] = np.stack([rng.uniform(-13, 13, k), rng.choice([0.65, 5.6], k), rng.choice([-4.6, 4.6], k)], axis=1).astype(np.float32) - o[:k]
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+
+    def start(seed, spheres):
+        scene = Scene().build("atrium", 6400, 0, 0.0, seed)
+        for s in range(spheres):
+            scene.add_sphere_mesh(s, 100 + s, quality=3)
+        scene.set_aspect(w / h)
+        return scene, scene.view(w, h), HipBackend.init(w, h, 1.0, max_path_length=2), Oracle(w, h, threads=4, max_path_length=2)
+
+    def step(scene, view, be, orc, edit, want, what):
+        edit()
+        scene.sync(be)
+        scene.mark_all_changed(); scene.sync(orc)           # the oracle rebuilds everything
+        got = [int(x) for x in be.debug_read("build_counters", 20).view(np.uint32)[:4]]
+        assert got == want, (what, got)
+        g, r = be.intersect(o, d), orc.intersect(o, d)
+        hit = r["inst"] >= 0
+        assert hit.mean() > 0.5, what
+        assert np.array_equal(g["inst"], r["inst"]) and np.array_equal(g["tri"], r["tri"]), what
+        assert np.array_equal(g["t"][hit].view(np.uint32), r["t"][hit].view(np.uint32)), what
+        be.reset_accumulation(); orc.reset()
+        be.render(view); orc.render(view)
+        assert np.array_equal(be.accumulator().view(np.uint32), orc.accumulator().view(np.uint32)), what
+
+    def two_at_once(scene):
+        scene.replace_mesh_with_sphere(2, 1, 79, quality=3)
+        scene.replace_mesh_with_sphere(4, 3, 80, quality=3)
+
+    # A: five meshes
+    scene, view, be, orc = start(11, 4)
+    assert scene.counts()["meshes"] == 5 and scene.triangle_count == 11502
+    step(scene, view, be, orc, lambda: None, [1, 0, 0, 0], "full build, forest, plain upload")
+    step(scene, view, be, orc, scene.mark_all_changed, [2, 0, 1, 5], "full build, forest, heads first")
+    step(scene, view, be, orc, scene.mark_all_changed, [3, 0, 2, 5], "full build, forest, heads first, again")
+    step(scene, view, be, orc, lambda: scene.replace_mesh_with_sphere(2, 1, 77, quality=3), [3, 1, 2, 5], "incremental, in place")
+    step(scene, view, be, orc, lambda: scene.replace_mesh_with_sphere(3, 2, 78, quality=4), [3, 2, 2, 4], "incremental, the mesh grows and is appended")
+    step(scene, view, be, orc, lambda: two_at_once(scene), [3, 3, 2, 4], "incremental, two meshes on the lanes")
+    be.close()
+    # B: mesh by mesh on the lanes, from the heads, the packets made behind the records
+    monkeypatch.setenv("RFW_NO_FOREST", "1")
+    scene, view, be, orc = start(11, 4)
+    monkeypatch.delenv("RFW_NO_FOREST")
+    step(scene, view, be, orc, lambda: None, [1, 0, 0, 0], "full build, lanes, plain upload")
+    step(scene, view, be, orc, scene.mark_all_changed, [2, 0, 1, 5], "full build, lanes, heads first")
+    be.close()
+    # C: one large mesh re-sent: the incremental build, heads first, nothing synchronised in between
+    scene, view, be, orc = start(5, 0)
+    assert scene.counts()["meshes"] == 1 and scene.triangle_count == 6382
+    step(scene, view, be, orc, lambda: None, [1, 0, 0, 0], "one mesh, full build")
+    for k in range(1, 4):
+        step(scene, view, be, orc, scene.mark_all_changed, [1, k, k, 1], f"one mesh re-sent, heads first, {k}")
+    be.close()
+
+
 def test_backends_one_after_the_other_in_one_process():
     """Every builder x (no frame slots, three) on small scenes, one backend after the other in ONE process, two frames back to back against the
     oracle.  A later backend gets device memory an earlier one has used: what a fresh process hands out zeroed is not zero here.  Found by
