@@ -206,7 +206,19 @@ RFW_HIP_API int rfw_hip_synchronize(void* instance);
  * (read_accumulator*, download_frame what = 1) stays the raw sum.  Out of scope: rfw_hip_render_batch (its frames finalise unfiltered) and
  * world > 1 or any exchange of tiles (the guides stay on their ranks: the frame finalises unfiltered, as FILTERED_SSAO finalises as SSAO
  * there); modes 1-6 ignore the option.  Setting either option to a different value restarts accumulation.  The filter assumes a finite
- * accumulator ("clamp_value"); a NaN or Inf pixel is skipped as a tap and spoils only itself. */
+ * accumulator ("clamp_value"); a NaN or Inf pixel is skipped as a tap and spoils only itself.
+ * Option "sample_offset" = s (an integer 0 ... 2^24, default 0): the samples of every image take the indices s, s + 1, ... for their seeds
+ * and the blue-noise sequence, while the sample COUNT (the frame's divisor, rfw_hip_frame_stats.sample_count) still starts at 0; modes 1-6
+ * honour it, rfw_hip_render_batch keeps index 0.  A different value starts a new image.
+ * Option "denoise_temporal" = Hmax (0 = off, the default; 1 ... 64, the longest history in samples): where "denoise" >= 1 acts, and only
+ * there, the filter's input is first blended with the previous image's, fetched where this pixel's primary hit lay in the previous view and
+ * kept where the geometry agrees (DESIGN.md "Denoiser: temporal"); the history is per instance, shared by its frame slots.  While it is on,
+ * image c since the history was dropped starts at sample index "sample_offset" + (c & 255), so that successive images of a camera that
+ * stands still draw different noise.  The history is dropped by a different value of the option, by rfw_hip_resize and with the instance —
+ * not by rfw_hip_reset_accumulation or a change of view, scene, mode, "denoise" or "denoise_colour": those start the images it links.
+ * Frames of modes 1-6 neither read nor write it.  Out of scope: motion vectors for moving instances (their pixels keep their history only
+ * while the plane and normal tests still pass, else they fall back to the spatial filter), variance estimation, rfw_hip_render_batch and
+ * sharded frames (unfiltered, as above). */
 enum {
     RFW_HIP_RENDER_DEFAULT = 0,
     RFW_HIP_RENDER_NORMAL = 1,
@@ -235,8 +247,9 @@ RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
 /* Options (unknown keys are an error).  The trait has none: these are the knobs a host outside the trait may turn.
  *   rendering      "max_path_length" (1 = primary + shadow), "clamp_value", "nee" (0 / 1), "sample_count", "sky_r" / "sky_g" / "sky_b",
  *                  "texture_array" (gpu-rt's 1024^2 x 5 texture array, default 1), "ao_samples" / "ao_radius" (render modes 5, 6),
- *                  "denoise" 0 (off, default) | 1 ... 5 a-trous passes over the path-traced frame, "denoise_colour" (> 0) — any other value
- *                  of either is RFW_HIP_E_INVALID; see rfw_hip_render
+ *                  "denoise" 0 (off, default) | 1 ... 5 a-trous passes over the path-traced frame, "denoise_colour" (> 0),
+ *                  "denoise_temporal" 0 (off, default) | 1 ... 64 samples of history across images, "sample_offset" 0 (default) ... 2^24,
+ *                  the first sample index of every image — any other value of these is RFW_HIP_E_INVALID; see rfw_hip_render
  *   measurement    "count_traversal" (node / triangle / instance counters of the next frames), "timing" (HIP events per kernel),
  *                  "denoise_form" 0 | 1 | 2 (the a-trous kernel form: the faster one per step | direct | tiled; the image is the same)
  *   ray order      "shadow_order" 0 | 1 | 2 (which end any-hit traversals start from; the image is the same under every order),
@@ -351,7 +364,10 @@ RFW_HIP_API int rfw_hip_occludes4(void* instance, const float* origin_xyz4, cons
 /* Debug read-back of the wavefront queues after the last render() bounce `bounce`
  * (test-only; enabled by option "keep_queues"=1).  Layout documented in DESIGN.md.
  * "dn_guide" (option "denoise"): the guide of the latest denoised frame, three float4 planes of width * height frame pixels, plane after
- * plane: (faced geometric normal, t), (hit point, 0), (albedo, f) with f = 1 where the pixel is filtered, 0 where it passes through. */
+ * plane: (faced geometric normal, t), (hit point, 0), (albedo, f) with f = 1 where the pixel is filtered, 0 where it passes through.
+ * "dn_history" (option "denoise_temporal"): the history plane the latest denoised frame wrote, width * height float4 (x.rgb, h): the blended
+ * demodulated radiance the a-trous passes started from and the samples behind it (0 where the pixel passes through); nothing before the
+ * first temporal frame. */
 RFW_HIP_API int rfw_hip_debug_read(void* instance, const char* what, void* dst, uint64_t bytes, uint64_t* written);
 
 /* occludes() that also reports how many 4-wide nodes each any-hit traversal visited (the any-hit counterpart of rfw_hip_depth_test).  For

@@ -507,3 +507,9 @@ class HipBackend:
         """The denoiser's guide of the latest frame (option "denoise"): g0 = (faced gN, t), g1 = (P, 0), g2 = (albedo, f), each (H, W, 4)."""
         g = np.frombuffer(self.debug_read("dn_guide", 48 * self.width * self.height).tobytes(), np.float32)
         return tuple(g.reshape(3, self.height, self.width, 4))
+
+    def denoise_history(self):
+        """The history plane the latest denoised frame wrote (option "denoise_temporal"): (H, W, 4) = (x.rgb, h), the blended demodulated
+        radiance and the samples behind it; empty before the first temporal frame."""
+        g = np.frombuffer(self.debug_read("dn_history", 16 * self.width * self.height).tobytes(), np.float32)
+        return g.reshape(-1, self.width, 4)

@@ -140,7 +140,7 @@ CameraParams camera_params(const Instance* I, const rfw_camera_view_3d& v, uint3
     c.clamp_value = I->clamp_value;
     c.p1[0] = v.p1.x; c.p1[1] = v.p1.y; c.p1[2] = v.p1.z;
     c.width = I->width; c.height = I->height;
-    c.sample_count = I->sample_count;
+    c.sample_count = I->image_offset + I->sample_count; // the sample's INDEX (seeds, blue noise); the finalisers get the count I->sample_count
     const Instance* S = scene_of(I);
     c.point_light_count = (uint32_t)S->point_lights.size();
     c.area_light_count = (uint32_t)S->area_lights.size();
@@ -275,6 +275,23 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         HIP_TRY(I, I->d_dn_guide.ensure(3 * px));
         for (int q = 0; q < 2 && I->denoise > 1; q++) HIP_TRY(I, I->d_dn_plane[q].ensure(px));
     }
+    // option "denoise_temporal": acts where the filter does.  Option "sample_offset": where an image starts, its first sample index is fixed
+    // (a batch of frames keeps index 0); the kernels clear the accumulator at index 0 only, so an image that starts elsewhere is cleared here
+    Instance* const O = scene_of(I);
+    const bool dnt = dn && O->denoise_temporal > 0;
+    const bool new_image = I->sample_count == 0;
+    if (new_image) {
+        I->image_offset = (k > 1 && !samples) ? 0u : O->sample_offset;
+        if (dnt) {
+            I->dn_image = O->dn_images++;
+            I->image_offset += I->dn_image & 255u;
+        }
+    }
+    if (dnt) {
+        const size_t px = (size_t)I->width * I->height;
+        for (int q = 0; q < 2; q++) HIP_TRY(I, O->d_dn_history[q].ensure(3 * px));
+        if (!O->dn_chain) HIP_TRY(I, hipEventCreateWithFlags(&O->dn_chain, hipEventDisableTiming));
+    }
 
     if (tm) (void)hipEventRecord(I->events[EV_FRAME0], main);
     // queue counters: this frame takes the block the previous frame's k_primary cleared (alloc_paths cleared both), and clears the other
@@ -296,6 +313,7 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         sc[s].spill = I->d_spill.ptr + (size_t)s * (I->cap_v + kSpillMargin);
         p[s] = path_dev(I, s);
         cam[s] = camera_params(I, view, s);
+        if (new_image && I->image_offset != 0u) HIP_TRY(I, hipMemsetAsync(p[s].acc, 0, (size_t)I->cap_v * sizeof(float4), st[s]));
         {   // k_shade's workgroup size (kernels.hip, k_shade): small where other frames' kernels share the chip with this call
             const Instance* O = scene_of(I);
             const int g = O->shade_group;
@@ -309,7 +327,7 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         if (scene_of(I)->stream_auto) cam[0].stream_run = scene_of(I)->stream_run;
         p[0].capacity = I->cap_v * k;
         for (uint32_t f = 0; f < k; f++) {
-            cam[0].batch_sample[f] = samples ? I->sample_count + f : 0u;
+            cam[0].batch_sample[f] = samples ? I->image_offset + I->sample_count + f : 0u;
             FrameView& v = bv.v[f];
             v.pos[0] = views[f].pos.x; v.pos[1] = views[f].pos.y; v.pos[2] = views[f].pos.z; v.lens_size = views[f].lens_size;
             v.right[0] = views[f].right.x; v.right[1] = views[f].right.y; v.right[2] = views[f].right.z; v.pad0 = 0.0f;
@@ -422,8 +440,23 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
     {
         if (dn) {
             float4* const planes[2] = {I->d_dn_plane[0].ptr, I->d_dn_plane[1].ptr};
+            const float4* x0 = nullptr;
+            if (dnt) { // behind the filter stage of the image before: it wrote the history this one reads, and read the one this one writes
+                const uint32_t h = I->dn_image & 1u;
+                if (O->dn_chain_pending) HIP_TRY(I, hipStreamWaitEvent(main, O->dn_chain, 0));
+                const float v[12] = {view.pos.x, view.pos.y, view.pos.z, view.p1.x, view.p1.y, view.p1.z, view.right.x, view.right.y, view.right.z, view.up.x, view.up.y, view.up.z};
+                std::memcpy(O->dn_view[h], v, sizeof(v));
+                launch_dn_temporal(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_dn_guide.ptr, I->dn_image ? O->d_dn_history[h ^ 1u].ptr : nullptr, O->d_dn_history[h].ptr,
+                                   O->dn_view[h ^ 1u], I->sample_count, O->denoise_temporal);
+                O->dn_latest = h;
+                x0 = O->d_dn_history[h].ptr;
+            }
             launch_atrous(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_dn_guide.ptr, planes, I->d_frame_out.ptr, I->sample_count, I->denoise, I->denoise_colour,
-                          I->denoise_form);
+                          I->denoise_form, x0);
+            if (dnt) {
+                HIP_TRY(I, hipEventRecord(O->dn_chain, main));
+                O->dn_chain_pending = true;
+            }
         }
         else if (mode == RFW_HIP_RENDER_FILTERED_SSAO) launch_ao_filter(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_ao_guide.ptr, I->d_frame_out.ptr, I->sample_count);
         else launch_assemble(main, cam[0], I->d_acc_slab.ptr, false, false, I->cap_v, I->d_frame_out.ptr, I->sample_count, mode != RFW_HIP_RENDER_DEFAULT);
@@ -634,6 +667,8 @@ void rfw_hip_destroy(void* inst)
         for (int h = 0; h < 2; h++) { I->d_ray_o[h].release(); I->d_ray_d[h].release(); I->d_thr[h].release(); I->d_hit[h].release(); }
         I->d_sh_o.release(); I->d_sh_d.release(); I->d_sh_e.release(); I->d_acc_slab.release(); I->d_frame_acc.release(); I->d_frame_out.release(); I->d_present.release();
         I->d_dn_guide.release(); I->d_dn_plane[0].release(); I->d_dn_plane[1].release();
+        I->d_dn_history[0].release(); I->d_dn_history[1].release();
+        if (I->dn_chain) (void)hipEventDestroy(I->dn_chain);
         for (auto& ev : I->ring)
             if (ev) (void)hipEventDestroy(ev);
         if (I->ev_fork) (void)hipEventDestroy(I->ev_fork);
@@ -730,6 +765,7 @@ int rfw_hip_resize(void* inst, uint32_t w, uint32_t h, double)
     I->restart = true;
     I->width = w;
     I->height = h;
+    I->dn_images = 0; // option "denoise_temporal": the history belongs to the old size
     // a gathered frame not de-tiled yet belongs to the old size (and d_recv may move below): forget it (each slot passes here for itself)
     I->deferred = Instance::Deferred(); I->acc_source = nullptr; I->presented_valid = false;
     const int arc = alloc_paths(I); // also restarts accumulation (gpu-rt/src/lib.rs:1809)
@@ -805,6 +841,21 @@ int rfw_hip_set_option(void* inst, const char* key, double value)
             if ((float)value == I->denoise_colour) return RFW_HIP_OK;
             I->denoise_colour = (float)value;
         }
+        I->sample_count = 0;
+        I->restart = true;
+    }
+    else if (k == "sample_offset") { // the first sample index of every image (seeds, blue noise); the sample COUNT still starts at 0.  A changed value starts a new image
+        if (!(value >= 0.0 && value <= 16777216.0) || value != std::floor(value)) return fail(I, RFW_HIP_E_INVALID, "set_option: sample_offset is an integer 0 ... 2^24");
+        if ((uint32_t)value == I->sample_offset) return RFW_HIP_OK;
+        I->sample_offset = (uint32_t)value;
+        I->sample_count = 0;
+        I->restart = true;
+    }
+    else if (k == "denoise_temporal") { // Hmax, the longest history in samples (denoise.inc, k_dn_temporal); a changed value drops the history and starts a new image
+        if (!(value >= 0.0 && value <= (double)kDenoiseMaxHistory) || value != std::floor(value)) return fail(I, RFW_HIP_E_INVALID, "set_option: denoise_temporal is 0 (off) or 1 ... 64 samples");
+        if ((uint32_t)value == I->denoise_temporal) return RFW_HIP_OK;
+        I->denoise_temporal = (uint32_t)value;
+        I->dn_images = 0;
         I->sample_count = 0;
         I->restart = true;
     }

@@ -483,6 +483,21 @@ struct Instance {
     float denoise_colour = kDenoiseDefaultColour;
     uint32_t denoise_form = 0;
     DevBuf<float4> d_dn_guide, d_dn_plane[2];
+    // option "sample_offset" (owner): the first sample index of every image; per slot: the one the image it accumulates started at (with
+    // "denoise_temporal" on: + the image's number & 255, so that successive images draw different noise)
+    uint32_t sample_offset = 0;
+    uint32_t image_offset = 0;
+    // option "denoise_temporal" (owner; DESIGN.md "Denoiser: temporal"): Hmax (0 = off), the two histories used in turn (three planes each:
+    // (x.rgb, h), g0, g1) with the view of the frame that wrote them (pos, p1, right, up), allocated at the first temporal frame; dn_images
+    // counts the images since the history was dropped (image c writes history c & 1 from history (c - 1) & 1), dn_latest is the history the
+    // latest temporal frame wrote.  The filter stages of successive images are chained through dn_chain, whichever slots' streams they run on.
+    uint32_t denoise_temporal = 0;
+    DevBuf<float4> d_dn_history[2];
+    float dn_view[2][12] = {};
+    uint32_t dn_images = 0, dn_latest = 0;
+    uint32_t dn_image = 0;             // per slot: the number of the image it accumulates
+    hipEvent_t dn_chain = nullptr;
+    bool dn_chain_pending = false;
     std::vector<hipEvent_t> ring;  // [kTimingRing][substreams][kNumEvents]
     hipEvent_t* events = nullptr;   // event set of the current frame, sub-shard 0
     uint32_t substreams = 1;        // the frame's tiles are dealt to this many sub-shards, each traced on its own stream

@@ -238,7 +238,7 @@ int rfw_hip_debug_lbvh_stress(void* inst, uint32_t n, uint32_t iterations, uint3
 
 // what: "hit0"/"hit1" (uint4), "ray_o0"/"ray_o1", "ray_d0"/"ray_d1", "thr0"/"thr1", "sh_o", "sh_d", "sh_e" (float4), "counters",
 //       "xforms" (InstanceXform), "normals" (InstanceNormal), "ao_rays", "ao_guide" (render modes 5, 6: DESIGN.md "Render modes"),
-//       "dn_guide" (option "denoise": DESIGN.md "Denoiser")
+//       "dn_guide" (option "denoise": DESIGN.md "Denoiser"), "dn_history" (option "denoise_temporal": DESIGN.md "Denoiser: temporal")
 int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, uint64_t* written)
 {
     LOCK(inst);
@@ -251,6 +251,14 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
         const uint32_t v[5] = {I->full_builds, I->incremental_builds, I->heads_first_builds, pinned, I->tlas_fused_builds}; // ([4]: instance updates through the fused TLAS path)
         const uint64_t n = std::min<uint64_t>(bytes, sizeof(v));
         std::memcpy(dst, v, n);
+        if (written) *written = n;
+        return RFW_HIP_OK;
+    }
+    if (w == "dn_history") { // owner state: the plane (x.rgb, h) the latest temporal frame wrote, whichever slot ran it
+        const uint64_t n = std::min<uint64_t>(bytes, (uint64_t)std::min<size_t>((size_t)I->width * I->height, I->d_dn_history[I->dn_latest].cap) * 16);
+        HIP_TRY(I, hipStreamSynchronize(I->stream));
+        for (Instance* c : I->slots) HIP_TRY(I, hipStreamSynchronize(c->stream));
+        if (n) HIP_TRY(I, hipMemcpy(dst, I->d_dn_history[I->dn_latest].ptr, n, hipMemcpyDeviceToHost));
         if (written) *written = n;
         return RFW_HIP_OK;
     }

@@ -8,6 +8,10 @@
 //               frame with f(q) = 1.  The first pass reads the accumulator slab and demodulates (x_0 = (acc / n) / max(albedo, kDnAlbedoFloor)),
 //               the last one remodulates, takes k_assemble's square root and writes the frame; pixels with f = 0 pass through with k_assemble's
 //               finalise.  Between passes x travels in float4 planes whose w holds f.
+//   k_dn_temporal  option "denoise_temporal" (DESIGN.md "Denoiser: temporal"), between the trace and the passes: x_0 of this image blended with
+//               the previous image's x_0, fetched where this pixel's primary hit lay in the previous view and weighted by the a-trous normal
+//               and plane weights; the result (x.rgb, h) and the frame's (g0, g1) are the history the next image reads.  The passes then start
+//               from that plane as passes after the first do (h > 0 exactly where f = 1 and x is finite).
 //
 // Two forms of a pass.  DIRECT: one thread per pixel, 25 taps straight from memory.  TILED: for step s the pixels with equal (x mod s, y mod s)
 // form s^2 sub-images on each of which the pass is a dense 5 x 5 filter; a workgroup takes 16 x 16 pixels of ONE sub-image and stages their
@@ -18,6 +22,7 @@
 constexpr float kDnPlane = 0.02f;       // wp = max(0, 1 - |dot(gN_p, P_q - P_p)| / (kDnPlane t_p)): distance from p's tangent plane, relative to the viewing distance
 constexpr int kDnNormalSquarings = 5;   // wn = max(0, dot(gN_p, gN_q))^32
 constexpr float kDnAlbedoFloor = 1e-3f; // demodulation divides by max(albedo, this) per channel
+constexpr float kDnTemporalMinWeight = 0.25f; // a reprojected pixel keeps its history while the weights of its four taps sum to this (of at most 1)
 constexpr int kDnTile = 16, kDnRadius = 2, kDnSpan = kDnTile + 2 * kDnRadius, kDnPitch = 32;
 constexpr float kDnH[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
 // which form pass i (step 2^i) takes unless option "denoise_form" forces one.  Timed per step at 1080p on the MI355X (EXPERIMENTS.md, "denoiser"):
@@ -177,6 +182,90 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_atrous(const CameraParams
     dp.out[i] = out;
 }
 
+// One history: three planes of width x height, (x.rgb, h), g0 = (gN, t) and g1 = (P, 0) of the frame that wrote it; h = samples behind x, 0 = none
+struct DnTemporalParams {
+    const float4* acc;    // as DnParams
+    uint64_t slab_elems;
+    const float4* guide;  // this frame's g0, g1, g2
+    const float4* prev;   // the previous image's history, or null: there is none
+    float4* cur;          // this image's
+    float pos[3], p1[3], right[3], up[3]; // the view of the frame that wrote prev
+    uint32_t samples;     // n, the sample just traced included
+    float max_history;    // Hmax
+};
+
+__global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal(const CameraParams cam, const DnTemporalParams tp)
+{
+    const int px = (int)(blockIdx.x * kDnTile + threadIdx.x % kDnTile), py = (int)(blockIdx.y * kDnTile + threadIdx.x / kDnTile);
+    if (px >= (int)cam.width || py >= (int)cam.height) return;
+    const int W = (int)cam.width, H = (int)cam.height;
+    const size_t plane = (size_t)cam.width * cam.height;
+    const uint32_t i = (uint32_t)px + (uint32_t)py * cam.width;
+    const float4 g0 = tp.guide[i], g1 = tp.guide[plane + i], g2 = tp.guide[2u * plane + i];
+    tp.cur[plane + i] = g0;
+    tp.cur[2u * plane + i] = g1;
+    if (!(g2.w > 0.0f)) {
+        tp.cur[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    uint32_t owner;
+    const uint32_t slot = pixel_to_slab(cam, (uint32_t)px, (uint32_t)py, owner);
+    const float4 a = tp.acc[(uint64_t)owner * tp.slab_elems + slot];
+    const float n = (float)(int)tp.samples;
+    const f3 c = mk3((a.x * 1.0f / n) / gl_max(g2.x, kDnAlbedoFloor), (a.y * 1.0f / n) / gl_max(g2.y, kDnAlbedoFloor), (a.z * 1.0f / n) / gl_max(g2.z, kDnAlbedoFloor));
+    f3 x = c;
+    float hh = 0.0f;
+    if (tp.prev != nullptr) {
+        // where the primary hit P lay in the previous view: the ray pos' -> P cut with the image plane through p1' spanned by right', up'
+        const f3 pos = mk3(tp.pos[0], tp.pos[1], tp.pos[2]), p1 = mk3(tp.p1[0], tp.p1[1], tp.p1[2]);
+        const f3 right = mk3(tp.right[0], tp.right[1], tp.right[2]), up = mk3(tp.up[0], tp.up[1], tp.up[2]);
+        const f3 P = mk3(g1.x, g1.y, g1.z), d = P - pos, nrm = cross(right, up);
+        const float num = dot(nrm, p1 - pos), den = dot(nrm, d);
+        if (num * den > 0.0f) { // (else behind the previous camera)
+            const f3 q = pos + (num / den) * d - p1;
+            const float u = dot(q, right) / dot(right, right), v = dot(q, up) / dot(up, up);
+            const float fx = u * (float)W - 0.5f, fy = v * (float)H - 0.5f;
+            if (fx > -1.0f && fx < (float)W && fy > -1.0f && fy < (float)H) { // (else no tap inside the frame; a NaN lands here too)
+                const float ffx = __builtin_floorf(fx), ffy = __builtin_floorf(fy);
+                const int i0 = (int)ffx, j0 = (int)ffy;
+                const float tx = fx - ffx, ty = fy - ffy;
+                const float inv_plane = 1.0f / (kDnPlane * g0.w);
+                float sw = 0.0f, sh = 0.0f;
+                f3 sx = mk3(0.0f);
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int e = 0; e < 2; e++) {
+                        const int qx = i0 + e, qy = j0 + b;
+                        if (qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+                        const uint32_t k = (uint32_t)qx + (uint32_t)qy * cam.width;
+                        const float4 xq = tp.prev[k];
+                        if (!(xq.w > 0.0f)) continue;
+                        const float4 g0q = tp.prev[plane + k], g1q = tp.prev[2u * plane + k];
+                        float wn = gl_max(0.0f, g0.x * g0q.x + g0.y * g0q.y + g0.z * g0q.z);
+                        for (int r = 0; r < kDnNormalSquarings; r++) wn = wn * wn;
+                        const float dp = g0.x * (g1q.x - g1.x) + g0.y * (g1q.y - g1.y) + g0.z * (g1q.z - g1.z);
+                        const float wp = gl_max(0.0f, 1.0f - gl_abs(dp) * inv_plane);
+                        const float w = (e ? tx : 1.0f - tx) * (b ? ty : 1.0f - ty) * wn * wp;
+                        sw += w;
+                        sx = sx + w * mk3(xq.x, xq.y, xq.z);
+                        sh += w * xq.w;
+                    }
+                if (sw >= kDnTemporalMinWeight) {
+                    hh = gl_min(sh / sw, gl_max(tp.max_history - n, 0.0f));
+                    if (hh > 0.0f) {
+                        const f3 xh = mk3(sx.x / sw, sx.y / sw, sx.z / sw);
+                        x = xh + (n / (hh + n)) * (c - xh);
+                    }
+                }
+            }
+        }
+    }
+    float h = hh + n;
+    if (!(gl_abs(x.x) <= 3.0e38f && gl_abs(x.y) <= 3.0e38f && gl_abs(x.z) <= 3.0e38f)) h = 0.0f; // not finite: no history for the next image, and the passes leave it out
+    tp.cur[i] = make_float4(x.x, x.y, x.z, h);
+}
+
 void launch_dn_guide(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, float4* guide, uint32_t pixel_mask)
 {
     if (p.capacity) hipLaunchKernelGGL(k_dn_guide, dim3((p.capacity + 255u) / 256u), dim3(256), 0, s, cam, sc, p, guide, pixel_mask);
@@ -195,22 +284,38 @@ template <bool TILED> static void launch_atrous_pass(hipStream_t s, const Camera
     else hipLaunchKernelGGL((k_atrous<false, false, TILED>), grid, block, 0, s, cam, dp);
 }
 
+void launch_dn_temporal(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, const float4* prev, float4* cur,
+                        const float prev_view[12], uint32_t samples, uint32_t max_history)
+{
+    DnTemporalParams tp;
+    tp.acc = acc;
+    tp.slab_elems = slab_elems;
+    tp.guide = guide;
+    tp.prev = prev;
+    tp.cur = cur;
+    for (int k = 0; k < 3; k++) { tp.pos[k] = prev_view[k]; tp.p1[k] = prev_view[3 + k]; tp.right[k] = prev_view[6 + k]; tp.up[k] = prev_view[9 + k]; }
+    tp.samples = samples;
+    tp.max_history = (float)max_history;
+    hipLaunchKernelGGL(k_dn_temporal, dim3(ceil_div(cam.width, kDnTile), ceil_div(cam.height, kDnTile)), dim3(kDnTile * kDnTile), 0, s, cam, tp);
+}
+
 void launch_atrous(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, float4* const planes[2], float4* frame,
-                   uint32_t samples, uint32_t passes, float sigma_colour, uint32_t form)
+                   uint32_t samples, uint32_t passes, float sigma_colour, uint32_t form, const float4* x0)
 {
     for (uint32_t i = 0; i < passes; i++) {
         DnParams dp;
         dp.acc = acc;
         dp.slab_elems = slab_elems;
         dp.guide = guide;
-        dp.in = i ? planes[(i - 1u) & 1u] : nullptr;
+        dp.in = i ? planes[(i - 1u) & 1u] : x0;
         dp.out = i + 1u == passes ? frame : planes[i & 1u];
         dp.samples = samples;
         dp.step_shift = i;
         const float sigma = (float)((double)sigma_colour / (double)(1u << i) / std::sqrt((double)samples));
         dp.inv_sigma2 = (float)std::min(1.0 / ((double)sigma * (double)sigma), 3.0e38); // (finite: 0 x inf would poison equal colours)
         const bool tiled = form == 0u ? atrous_tiled_by_default(i) : form == 2u;
-        if (tiled) launch_atrous_pass<true>(s, cam, dp, i == 0u, i + 1u == passes);
-        else launch_atrous_pass<false>(s, cam, dp, i == 0u, i + 1u == passes);
+        const bool first = i == 0u && x0 == nullptr; // (x_0 handed in: every pass reads a plane)
+        if (tiled) launch_atrous_pass<true>(s, cam, dp, first, i + 1u == passes);
+        else launch_atrous_pass<false>(s, cam, dp, first, i + 1u == passes);
     }
 }

@@ -114,11 +114,16 @@ void launch_ao_filter(hipStream_t s, const CameraParams& cam, const float4* acc,
 // (faced gN, t), (P, 0), (albedo, f); `pixel_mask` strips the sample index a batch of samples keeps above the pixel index of the path word.
 void launch_dn_guide(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, float4* guide, uint32_t pixel_mask);
 // `passes` (1 .. kDenoiseMaxPasses) a-trous passes from the accumulator slabs (as launch_assemble reads them) into `frame`, in place of
-// launch_assemble; planes[2]: width x height each, used when passes > 1.  form: 0 = the form measured to be faster per step, 1 direct, 2 tiled.
+// launch_assemble; planes[2]: width x height each, used when passes > 1; x0 (or null): x_0 as a plane (rgb, w > 0 where filtered).  form: 0 = the form measured to be faster per step, 1 direct, 2 tiled.
 constexpr uint32_t kDenoiseMaxPasses = 5;
 constexpr float kDenoiseDefaultColour = 32.0f; // option "denoise_colour" (sigma_c, demodulated radiance): chosen by the sweep in DESIGN.md "Denoiser"
 void launch_atrous(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, float4* const planes[2], float4* frame,
-                   uint32_t samples, uint32_t passes, float sigma_colour, uint32_t form);
+                   uint32_t samples, uint32_t passes, float sigma_colour, uint32_t form, const float4* x0 = nullptr);
+// option "denoise_temporal": before launch_atrous, which then takes `cur` as x0.  A history is three planes of width x height ((x.rgb, h), g0, g1);
+// prev = the previous image's (null: none) and prev_view = pos, p1, right, up of the frame that wrote it; max_history = Hmax, in samples.
+constexpr uint32_t kDenoiseMaxHistory = 64;
+void launch_dn_temporal(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, const float4* prev, float4* cur,
+                        const float prev_view[12], uint32_t samples, uint32_t max_history);
 void launch_eval_shading(hipStream_t s, const SceneDev& sc, const CameraParams& cam, int op, uint32_t n, const float* in, float* out);
 void launch_query_closest(hipStream_t s, const SceneDev& sc, const float* origins, const float* directions, float t_min, float t_max, uint64_t n,
                           rfw_hip_hit* hits, uint32_t* depth = nullptr /* optional: nodes visited per ray */);

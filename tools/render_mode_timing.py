@@ -7,7 +7,9 @@ quotes its output.
 
 --denoise 0,1,3,5 times mode 0 under option "denoise" instead (DESIGN.md "Denoiser"): the settings take turns, repeat by repeat, so that
 they share whatever else the machine is doing; --denoise-form 1 / 2 forces the direct / tiled kernel form; --bandwidth adds what
-rfw_hip_bandwidth_probe reads per second, the yardstick of a pass's 64 algorithmic bytes per pixel."""
+rfw_hip_bandwidth_probe reads per second, the yardstick of a pass's 64 algorithmic bytes per pixel.  --denoise-temporal H times every
+non-zero setting k a second time with option "denoise_temporal" = H (DESIGN.md "Denoiser: temporal"), in the same turns; every frame of a
+timed repeat then starts a new image (reset_accumulation), for both, since that is where the history acts."""
 import argparse
 import os
 import statistics
@@ -22,6 +24,7 @@ def main():
     ap.add_argument("--modes", default="0,5,6")
     ap.add_argument("--denoise", default="")
     ap.add_argument("--denoise-form", type=int, default=0)
+    ap.add_argument("--denoise-temporal", type=int, default=0)
     ap.add_argument("--max-path-length", type=int, default=None)  # 1 for the modes (DESIGN.md "Render modes"), 3 with --denoise
     ap.add_argument("--bandwidth", action="store_true")
     ap.add_argument("--width", type=int, default=1920)
@@ -44,24 +47,32 @@ def main():
     scene.sync(be)
     what = f"{a.repeats} x {a.frames} frames, {a.width}x{a.height}, atrium of {a.triangles} triangles, max path length {a.max_path_length}"
     if a.denoise:
-        settings = [int(k) for k in a.denoise.split(",")]
-        if any(settings):
+        passes = [int(k) for k in a.denoise.split(",")]
+        settings = [(k, 0) for k in passes] + [(k, a.denoise_temporal) for k in passes if k and a.denoise_temporal]
+        if any(passes):
             be.set_option("denoise_form", a.denoise_form)
-        runs = {k: [] for k in settings}
+        runs = {s: [] for s in settings}
         for rep in range(-1, a.repeats):  # (-1: the warm-up round of every setting)
-            for k in settings:
-                if any(settings):  # (all zero: never name the option, so that a library without it can be timed too)
+            for k, hmax in settings:
+                if any(passes):  # (all zero: never name the option, so that a library without it can be timed too)
                     be.set_option("denoise", k)
+                if a.denoise_temporal:
+                    be.set_option("denoise_temporal", hmax)
                 t0 = time.perf_counter()
                 for _ in range(a.warmup if rep < 0 else a.frames):
+                    if a.denoise_temporal:
+                        be.reset_accumulation()
                     be.render(view)
                 be.framebuffer()
                 if rep >= 0:
-                    runs[k].append((time.perf_counter() - t0) * 1e3 / a.frames)
-        for k in settings:
-            print(f"denoise {k} form {a.denoise_form}: {statistics.median(runs[k]):.3f} ms/frame (min {min(runs[k]):.3f}, max {max(runs[k]):.3f}; {what})", flush=True)
+                    runs[(k, hmax)].append((time.perf_counter() - t0) * 1e3 / a.frames)
+        for k, hmax in settings:
+            r = runs[(k, hmax)]
+            print(f"denoise {k} form {a.denoise_form}{f' temporal {hmax}' if hmax else ''}: {statistics.median(r):.3f} ms/frame (min {min(r):.3f}, max {max(r):.3f}; {what})", flush=True)
         if a.bandwidth:
-            print(f"bandwidth probe: {be.bandwidth_probe():.0f} GB/s (read + written); a pass moves 64 B x {a.width * a.height} pixels = {64e-6 * a.width * a.height:.1f} MB", flush=True)
+            px = a.width * a.height
+            print(f"bandwidth probe: {be.bandwidth_probe():.0f} GB/s (read + written); a pass moves 64 B x {px} pixels = {64e-6 * px:.1f} MB"
+                  + (f", k_dn_temporal at least 128 B x {px} = {128e-6 * px:.1f} MB" if a.denoise_temporal else ""), flush=True)
         be.close()
         return
     be.set_option("ao_samples", a.ao_samples)
