@@ -216,9 +216,14 @@ RFW_HIP_API int rfw_hip_synchronize(void* instance);
  * image c since the history was dropped starts at sample index "sample_offset" + (c & 255), so that successive images of a camera that
  * stands still draw different noise.  The history is dropped by a different value of the option, by rfw_hip_resize and with the instance —
  * not by rfw_hip_reset_accumulation or a change of view, scene, mode, "denoise" or "denoise_colour": those start the images it links.
- * Frames of modes 1-6 neither read nor write it.  Out of scope: motion vectors for moving instances (their pixels keep their history only
- * while the plane and normal tests still pass, else they fall back to the spatial filter), variance estimation, rfw_hip_render_batch and
- * sharded frames (unfiltered, as above). */
+ * Frames of modes 1-6 neither read nor write it.  Out of scope: variance estimation, rfw_hip_render_batch and sharded frames (unfiltered,
+ * as above).
+ * Option "denoise_motion" = 0 (off, the default) | 1: where "denoise_temporal" acts, and only there, a pixel's primary hit is first carried
+ * into the pose its instance had in the previous image (a rigid or affine instance matrix; DESIGN.md "Denoiser: motion"), and a tap of the
+ * previous image counts only where it shows the same instance.  An instance that is new, was removed in the previous image, changed its
+ * mesh or has a matrix whose last row is not (0, 0, 0, 1) starts without history.  With one instance in the scene, and whenever no matrix
+ * changes, the frame equals the one with the option off bit for bit.  A different value drops the history and starts a new image.  Skinned
+ * meshes follow their instance matrix only.  Off, nothing is allocated, launched or written for it. */
 enum {
     RFW_HIP_RENDER_DEFAULT = 0,
     RFW_HIP_RENDER_NORMAL = 1,
@@ -248,8 +253,9 @@ RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
  *   rendering      "max_path_length" (1 = primary + shadow), "clamp_value", "nee" (0 / 1), "sample_count", "sky_r" / "sky_g" / "sky_b",
  *                  "texture_array" (gpu-rt's 1024^2 x 5 texture array, default 1), "ao_samples" / "ao_radius" (render modes 5, 6),
  *                  "denoise" 0 (off, default) | 1 ... 5 a-trous passes over the path-traced frame, "denoise_colour" (> 0),
- *                  "denoise_temporal" 0 (off, default) | 1 ... 64 samples of history across images, "sample_offset" 0 (default) ... 2^24,
- *                  the first sample index of every image — any other value of these is RFW_HIP_E_INVALID; see rfw_hip_render
+ *                  "denoise_temporal" 0 (off, default) | 1 ... 64 samples of history across images, "denoise_motion" 0 (off, default) | 1
+ *                  the history follows moving instances, "sample_offset" 0 (default) ... 2^24, the first sample index of every
+ *                  image — any other value of these is RFW_HIP_E_INVALID; see rfw_hip_render
  *   measurement    "count_traversal" (node / triangle / instance counters of the next frames), "timing" (HIP events per kernel),
  *                  "denoise_form" 0 | 1 | 2 (the a-trous kernel form: the faster one per step | direct | tiled; the image is the same)
  *   ray order      "shadow_order" 0 | 1 | 2 (which end any-hit traversals start from; the image is the same under every order),
@@ -367,7 +373,14 @@ RFW_HIP_API int rfw_hip_occludes4(void* instance, const float* origin_xyz4, cons
  * plane: (faced geometric normal, t), (hit point, 0), (albedo, f) with f = 1 where the pixel is filtered, 0 where it passes through.
  * "dn_history" (option "denoise_temporal"): the history plane the latest denoised frame wrote, width * height float4 (x.rgb, h): the blended
  * demodulated radiance the a-trous passes started from and the samples behind it (0 where the pixel passes through); nothing before the
- * first temporal frame. */
+ * first temporal frame.
+ * "dn_ids" (option "denoise_motion"): width * height uint32 of the current frame slot, the instance id of the primary hit of the latest
+ * sample of every frame pixel, 0xffffffff where the camera ray missed; bounded by the allocation (nothing before the first frame with the
+ * option on, nothing after rfw_hip_resize).
+ * "dn_motion" (option "denoise_motion"): the records the latest temporal frame used, one of 96 bytes per instance id of that frame: the
+ * rows of A = M' inverse(M) (3 x 4 floats: a point of this image -> the same point of the instance in the previous image), then the rows
+ * of B = transpose(inverse(A)) (3 x 4 floats, of which [0][3] holds the uint32 state — 0 no history, 1 the matrix did not change, 2 moved —
+ * and [1][3], [2][3] are 0).  A and B are zero where the state is 0. */
 RFW_HIP_API int rfw_hip_debug_read(void* instance, const char* what, void* dst, uint64_t bytes, uint64_t* written);
 
 /* occludes() that also reports how many 4-wide nodes each any-hit traversal visited (the any-hit counterpart of rfw_hip_depth_test).  For

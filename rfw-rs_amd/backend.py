@@ -513,3 +513,17 @@ class HipBackend:
         radiance and the samples behind it; empty before the first temporal frame."""
         g = np.frombuffer(self.debug_read("dn_history", 16 * self.width * self.height).tobytes(), np.float32)
         return g.reshape(-1, self.width, 4)
+
+    def denoise_ids(self):
+        """The instance ids of the latest frame's primary hits (option "denoise_motion"): (H, W) uint32, 0xffffffff where the camera ray
+        missed; empty before the first frame with the option on."""
+        g = np.frombuffer(self.debug_read("dn_ids", 4 * self.width * self.height).tobytes(), np.uint32)
+        return g.reshape(-1, self.width)
+
+    def denoise_motion(self):
+        """The motion records the latest temporal frame used (option "denoise_motion"), one per instance id: (A, B, state) with A (n, 3, 4) the
+        rows of M' inverse(M), B (n, 3, 3) the rows of its inverse transpose and state (n,) uint32: 0 no history, 1 not moved, 2 moved."""
+        raw = self.debug_read("dn_motion", 96 * (1 << 20)).tobytes()
+        r = np.frombuffer(raw, np.float32).reshape(-1, 6, 4)
+        state = np.frombuffer(raw, np.uint32).reshape(-1, 24)[:, 15].copy()
+        return r[:, :3, :].copy(), r[:, 3:, :3].copy(), state

@@ -292,6 +292,13 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         for (int q = 0; q < 2; q++) HIP_TRY(I, O->d_dn_history[q].ensure(3 * px));
         if (!O->dn_chain) HIP_TRY(I, hipEventCreateWithFlags(&O->dn_chain, hipEventDisableTiming));
     }
+    // option "denoise_motion": acts where the temporal option does
+    const bool dnm = dnt && O->denoise_motion > 0;
+    if (dnm) {
+        const size_t px = (size_t)I->width * I->height;
+        HIP_TRY(I, I->d_dn_ids.ensure(px));
+        for (int q = 0; q < 2; q++) HIP_TRY(I, O->d_dn_history_ids[q].ensure(px));
+    }
 
     if (tm) (void)hipEventRecord(I->events[EV_FRAME0], main);
     // queue counters: this frame takes the block the previous frame's k_primary cleared (alloc_paths cleared both), and clears the other
@@ -390,6 +397,7 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
                     g.capacity = I->cap_v;
                 }
                 launch_dn_guide(st[s], cam[s], sc[s], g, I->d_dn_guide.ptr, k > 1 ? 0x00ffffffu : 0xffffffffu);
+                if (dnm) launch_dn_ids(st[s], cam[s], g, I->d_dn_ids.ptr, k > 1 ? 0x00ffffffu : 0xffffffffu);
             }
         }
         for (uint32_t s = 0; s < S; s++) {
@@ -446,8 +454,23 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
                 if (O->dn_chain_pending) HIP_TRY(I, hipStreamWaitEvent(main, O->dn_chain, 0));
                 const float v[12] = {view.pos.x, view.pos.y, view.pos.z, view.p1.x, view.p1.y, view.p1.z, view.right.x, view.right.y, view.right.z, view.up.x, view.up.y, view.up.z};
                 std::memcpy(O->dn_view[h], v, sizeof(v));
+                DnMotionLaunch ml{};
+                if (dnm) { // the snapshot of the TLAS this frame traced with, and the records against the previous image's
+                    Instance* const T = tlas_of(I);
+                    const uint32_t n_inst = (uint32_t)T->n_instances;
+                    HIP_TRY(I, O->d_dn_snapshot[h].ensure(std::max<size_t>(n_inst, 1) * kDnInstanceBytes));
+                    HIP_TRY(I, O->d_dn_motion.ensure(std::max<size_t>(n_inst, 1) * kDnMotionBytes));
+                    launch_dn_motion(main, T->d_forward, T->d_xforms.ptr, T->d_normals.ptr, n_inst, I->dn_image ? O->d_dn_snapshot[h ^ 1u].ptr : nullptr,
+                                     O->dn_snap_count[h ^ 1u], O->d_dn_snapshot[h].ptr, O->d_dn_motion.ptr);
+                    O->dn_snap_count[h] = O->dn_motion_count = n_inst;
+                    ml.ids = I->d_dn_ids.ptr;
+                    ml.prev_ids = I->dn_image ? O->d_dn_history_ids[h ^ 1u].ptr : nullptr;
+                    ml.cur_ids = O->d_dn_history_ids[h].ptr;
+                    ml.records = O->d_dn_motion.ptr;
+                    ml.n_records = n_inst;
+                }
                 launch_dn_temporal(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_dn_guide.ptr, I->dn_image ? O->d_dn_history[h ^ 1u].ptr : nullptr, O->d_dn_history[h].ptr,
-                                   O->dn_view[h ^ 1u], I->sample_count, O->denoise_temporal);
+                                   O->dn_view[h ^ 1u], I->sample_count, O->denoise_temporal, dnm ? &ml : nullptr);
                 O->dn_latest = h;
                 x0 = O->d_dn_history[h].ptr;
             }
@@ -668,6 +691,8 @@ void rfw_hip_destroy(void* inst)
         I->d_sh_o.release(); I->d_sh_d.release(); I->d_sh_e.release(); I->d_acc_slab.release(); I->d_frame_acc.release(); I->d_frame_out.release(); I->d_present.release();
         I->d_dn_guide.release(); I->d_dn_plane[0].release(); I->d_dn_plane[1].release();
         I->d_dn_history[0].release(); I->d_dn_history[1].release();
+        I->d_dn_ids.release(); I->d_dn_motion.release();
+        for (int q = 0; q < 2; q++) { I->d_dn_history_ids[q].release(); I->d_dn_snapshot[q].release(); }
         if (I->dn_chain) (void)hipEventDestroy(I->dn_chain);
         for (auto& ev : I->ring)
             if (ev) (void)hipEventDestroy(ev);
@@ -766,6 +791,10 @@ int rfw_hip_resize(void* inst, uint32_t w, uint32_t h, double)
     I->width = w;
     I->height = h;
     I->dn_images = 0; // option "denoise_temporal": the history belongs to the old size
+    // option "denoise_motion": so do the ids, the snapshots and the records (allocated again at the next frame that needs them)
+    I->d_dn_ids.release(); I->d_dn_motion.release();
+    for (int q = 0; q < 2; q++) { I->d_dn_history_ids[q].release(); I->d_dn_snapshot[q].release(); I->dn_snap_count[q] = 0; }
+    I->dn_motion_count = 0;
     // a gathered frame not de-tiled yet belongs to the old size (and d_recv may move below): forget it (each slot passes here for itself)
     I->deferred = Instance::Deferred(); I->acc_source = nullptr; I->presented_valid = false;
     const int arc = alloc_paths(I); // also restarts accumulation (gpu-rt/src/lib.rs:1809)
@@ -855,6 +884,14 @@ int rfw_hip_set_option(void* inst, const char* key, double value)
         if (!(value >= 0.0 && value <= (double)kDenoiseMaxHistory) || value != std::floor(value)) return fail(I, RFW_HIP_E_INVALID, "set_option: denoise_temporal is 0 (off) or 1 ... 64 samples");
         if ((uint32_t)value == I->denoise_temporal) return RFW_HIP_OK;
         I->denoise_temporal = (uint32_t)value;
+        I->dn_images = 0;
+        I->sample_count = 0;
+        I->restart = true;
+    }
+    else if (k == "denoise_motion") { // the temporal option follows moving instances (denoise.inc, k_dn_temporal_motion); a changed value drops the history and starts a new image
+        if (value != 0.0 && value != 1.0) return fail(I, RFW_HIP_E_INVALID, "set_option: denoise_motion is 0 (off) or 1");
+        if ((uint32_t)value == I->denoise_motion) return RFW_HIP_OK;
+        I->denoise_motion = (uint32_t)value;
         I->dn_images = 0;
         I->sample_count = 0;
         I->restart = true;

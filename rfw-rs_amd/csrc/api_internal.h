@@ -498,6 +498,17 @@ struct Instance {
     uint32_t dn_image = 0;             // per slot: the number of the image it accumulates
     hipEvent_t dn_chain = nullptr;
     bool dn_chain_pending = false;
+    // option "denoise_motion" (owner; DESIGN.md "Denoiser: motion"): per slot the instance ids of the latest sample's primary hits; in the
+    // owner, next to each history, the ids and the instance snapshot (kDnInstanceBytes per instance, dn_snap_count of them) of the frame that
+    // wrote it, and the records (kDnMotionBytes per instance of the latest temporal frame, dn_motion_count of them) k_dn_motion made for it
+    uint32_t denoise_motion = 0;
+    DevBuf<uint32_t> d_dn_ids;
+    DevBuf<uint32_t> d_dn_history_ids[2];
+    DevBuf<char> d_dn_snapshot[2], d_dn_motion;
+    uint32_t dn_snap_count[2] = {}, dn_motion_count = 0;
+    // per TLAS holder (tlas_of): the forward matrices its instance descriptors were made from — d_matrices (the launch chain) or the
+    // matrices inside d_stage_dev (the fused path)
+    const rfw_mat4* d_forward = nullptr;
     std::vector<hipEvent_t> ring;  // [kTimingRing][substreams][kNumEvents]
     hipEvent_t* events = nullptr;   // event set of the current frame, sub-shard 0
     uint32_t substreams = 1;        // the frame's tiles are dealt to this many sub-shards, each traced on its own stream

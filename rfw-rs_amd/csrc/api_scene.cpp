@@ -844,6 +844,7 @@ int build_instances(Instance* I, Instance* T)
         if ((rc = ensure_lbvh_ws(T, n_valid))) return rc;
         HIP_TRY(I, hipMemcpyAsync(T->d_stage_dev.ptr, st, off_joints, hipMemcpyHostToDevice, s));
         const rfw_mat4* d_mats = reinterpret_cast<const rfw_mat4*>(T->d_stage_dev.ptr + off_mats);
+        T->d_forward = d_mats;
         const uint32_t* d_mesh_of = reinterpret_cast<const uint32_t*>(T->d_stage_dev.ptr + off_meshof);
         const uint32_t* d_valid = reinterpret_cast<const uint32_t*>(T->d_stage_dev.ptr + off_valid);
         const DevBox* d_local = reinterpret_cast<const DevBox*>(T->d_stage_dev.ptr + off_local);
@@ -859,6 +860,7 @@ int build_instances(Instance* I, Instance* T)
         I->tlas_fused_builds++;
         return RFW_HIP_OK;
     }
+    T->d_forward = T->d_matrices.ptr;
     if (n_all) {
         HIP_TRY(I, hipMemcpyAsync(T->d_matrices.ptr, mats, n_all * sizeof(rfw_mat4), hipMemcpyHostToDevice, s));
         HIP_TRY(I, hipMemcpyAsync(T->d_mesh_of_instance.ptr, mesh_of, n_all * 4, hipMemcpyHostToDevice, s));

@@ -12,6 +12,9 @@
 //               the previous image's x_0, fetched where this pixel's primary hit lay in the previous view and weighted by the a-trous normal
 //               and plane weights; the result (x.rgb, h) and the frame's (g0, g1) are the history the next image reads.  The passes then start
 //               from that plane as passes after the first do (h > 0 exactly where f = 1 and x is finite).
+//   k_dn_ids, k_dn_motion, k_dn_temporal_motion  option "denoise_motion" (DESIGN.md "Denoiser: motion"): the instance id of every pixel's primary
+//               hit, one record per instance that carries a point and a normal of this image into the instance's pose of the previous image,
+//               and k_dn_temporal reprojecting through that record, its taps restricted to the same instance.
 //
 // Two forms of a pass.  DIRECT: one thread per pixel, 25 taps straight from memory.  TILED: for step s the pixels with equal (x mod s, y mod s)
 // form s^2 sub-images on each of which the pass is a dense 5 x 5 filter; a workgroup takes 16 x 16 pixels of ONE sub-image and stages their
@@ -194,7 +197,94 @@ struct DnTemporalParams {
     float max_history;    // Hmax
 };
 
-__global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal(const CameraParams cam, const DnTemporalParams tp)
+constexpr uint32_t kDnNoId = 0xffffffffu; // id planes: the camera ray missed
+
+// option "denoise_motion".  Per frame pixel the instance id of the primary hit, next to k_dn_guide and with its bounds handling.
+__global__ __launch_bounds__(256) void k_dn_ids(const CameraParams cam, const PathDev p, uint32_t* __restrict__ ids, const uint32_t pixel_mask)
+{
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= p.capacity) return;
+    const uint4 S = p.hit[0][idx];
+    if (S.x == kNoPath) return; // a slab slot without a pixel
+    const uint32_t px = fbits(p.ray_o[0][idx].w) & pixel_mask;
+    if (px >= cam.width * cam.height) return;
+    ids[px] = (int32_t)S.x >= 0 ? S.x : kDnNoId;
+}
+
+// What a history keeps of every instance of the frame that wrote it, and what k_dn_motion makes of two of them
+struct alignas(16) DnInstance {
+    float m[16];       // the forward matrix M, column major (rfw_mat4)
+    float n[3][4];     // InstanceNormal: the rows of transpose(inverse(M))
+    uint32_t mesh, valid, pad[2]; // InstanceXform::mesh, flags & 1
+};
+static_assert(sizeof(DnInstance) == kDnInstanceBytes, "DnInstance");
+struct alignas(16) DnMotion {
+    float a[3][4];     // rows of A = M' inverse(M): a point of this image -> where the instance held it in the previous image
+    float b[3][4];     // rows of B = N' transpose(M) = transpose(inverse(A)) in [0..2]; [0][3] holds the state's bits, [1][3] = [2][3] = 0
+};
+static_assert(sizeof(DnMotion) == kDnMotionBytes, "DnMotion");
+
+// One thread per instance of this frame: its record, and its entry of the snapshot that travels with the history this image writes.
+// state 0 = no history (a new, removed or re-meshed instance, a matrix that is not affine, a record that is not finite), 1 = the matrix is the
+// previous image's bit for bit, 2 = moved.  Plain float32, every sum left to right.
+__global__ __launch_bounds__(64) void k_dn_motion(const rfw_mat4* __restrict__ matrices, const InstanceXform* __restrict__ xf, const InstanceNormal* __restrict__ nm,
+                                                  const uint32_t n, const DnInstance* __restrict__ prev, const uint32_t n_prev, DnInstance* __restrict__ cur,
+                                                  DnMotion* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    DnInstance c;
+    for (int k = 0; k < 16; k++) c.m[k] = matrices[i].m[k];
+    const InstanceXform x = xf[i];
+    const InstanceNormal nn = nm[i];
+    for (int k = 0; k < 4; k++) { c.n[0][k] = nn.n_r0[k]; c.n[1][k] = nn.n_r1[k]; c.n[2][k] = nn.n_r2[k]; }
+    c.mesh = x.mesh;
+    c.valid = x.flags & 1u;
+    c.pad[0] = c.pad[1] = 0u;
+    cur[i] = c;
+    DnMotion r;
+    for (int j = 0; j < 3; j++)
+        for (int k = 0; k < 4; k++) r.a[j][k] = r.b[j][k] = 0.0f;
+    uint32_t state = 0u;
+    if (prev != nullptr && i < n_prev) {
+        const DnInstance q = prev[i];
+        const auto affine = [](const float* m) { return fbits(m[3]) == 0u && fbits(m[7]) == 0u && fbits(m[11]) == 0u && fbits(m[15]) == 0x3f800000u; };
+        if (q.valid != 0u && c.valid != 0u && q.mesh == c.mesh && affine(q.m) && affine(c.m)) {
+            bool same = true;
+            for (int k = 0; k < 16; k++) same = same && fbits(q.m[k]) == fbits(c.m[k]);
+            const float* inv[3] = {x.inv_r0, x.inv_r1, x.inv_r2}; // row k of inverse(M); its fourth row is (0, 0, 0, 1)
+            bool finite = true;
+            for (int j = 0; j < 3; j++) {
+                for (int k = 0; k < 4; k++) { // row j of M' = (m'[j], m'[4 + j], m'[8 + j], m'[12 + j])
+                    float s = (q.m[j] * inv[0][k] + q.m[4 + j] * inv[1][k]) + q.m[8 + j] * inv[2][k];
+                    if (k == 3) s = s + q.m[12 + j];
+                    r.a[j][k] = s;
+                    finite = finite && gl_abs(s) <= 3.0e38f;
+                }
+                for (int k = 0; k < 3; k++) { // transpose(M)[l][k] = M[k][l] = m[4 l + k]
+                    const float s = (q.n[j][0] * c.m[k] + q.n[j][1] * c.m[4 + k]) + q.n[j][2] * c.m[8 + k];
+                    r.b[j][k] = s;
+                    finite = finite && gl_abs(s) <= 3.0e38f;
+                }
+            }
+            state = !finite ? 0u : same ? 1u : 2u;
+        }
+    }
+    r.b[0][3] = bitsf(state);
+    out[i] = r;
+}
+
+struct DnMotionParams {
+    const uint32_t* ids;      // this frame's instance ids
+    const uint32_t* prev_ids; // those of the frame that wrote tp.prev (null with it)
+    uint32_t* cur_ids;        // ... and that travel with tp.cur
+    const DnMotion* records;  // one per instance id of this frame
+    uint32_t n_records;
+};
+
+// k_dn_temporal and, with MOTION, k_dn_temporal_motion: there the hit (P, gN) is first carried into the previous image's pose of its instance
+// (state 2), a tap must show the same instance, and an instance without a record there (state 0) has no history.
+template <bool MOTION> RFW_DI void dn_temporal_pixel(const CameraParams& cam, const DnTemporalParams& tp, const DnMotionParams& mp)
 {
     const int px = (int)(blockIdx.x * kDnTile + threadIdx.x % kDnTile), py = (int)(blockIdx.y * kDnTile + threadIdx.x / kDnTile);
     if (px >= (int)cam.width || py >= (int)cam.height) return;
@@ -204,6 +294,11 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal(const CameraP
     const float4 g0 = tp.guide[i], g1 = tp.guide[plane + i], g2 = tp.guide[2u * plane + i];
     tp.cur[plane + i] = g0;
     tp.cur[2u * plane + i] = g1;
+    uint32_t id = kDnNoId;
+    if (MOTION) {
+        id = mp.ids[i];
+        mp.cur_ids[i] = id;
+    }
     if (!(g2.w > 0.0f)) {
         tp.cur[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
@@ -215,11 +310,27 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal(const CameraP
     const f3 c = mk3((a.x * 1.0f / n) / gl_max(g2.x, kDnAlbedoFloor), (a.y * 1.0f / n) / gl_max(g2.y, kDnAlbedoFloor), (a.z * 1.0f / n) / gl_max(g2.z, kDnAlbedoFloor));
     f3 x = c;
     float hh = 0.0f;
-    if (tp.prev != nullptr) {
+    f3 P = mk3(g1.x, g1.y, g1.z), N = mk3(g0.x, g0.y, g0.z);
+    bool history = tp.prev != nullptr;
+    if (MOTION && history) {
+        uint32_t state = 0u;
+        if (id < mp.n_records) { // (neighbouring pixels share an instance: a cached vector load, not uniform across the wavefront)
+            const float4* rp = reinterpret_cast<const float4*>(mp.records + id);
+            const float4 b0 = rp[3];
+            state = fbits(b0.w);
+            if (state == 2u) {
+                const float4 a0 = rp[0], a1 = rp[1], a2 = rp[2], b1 = rp[4], b2 = rp[5];
+                N = normalize(xform_rows(b0, b1, b2, N, 0.0f));
+                P = xform_rows(a0, a1, a2, P, 1.0f);
+            }
+        }
+        history = state != 0u;
+    }
+    if (history) {
         // where the primary hit P lay in the previous view: the ray pos' -> P cut with the image plane through p1' spanned by right', up'
         const f3 pos = mk3(tp.pos[0], tp.pos[1], tp.pos[2]), p1 = mk3(tp.p1[0], tp.p1[1], tp.p1[2]);
         const f3 right = mk3(tp.right[0], tp.right[1], tp.right[2]), up = mk3(tp.up[0], tp.up[1], tp.up[2]);
-        const f3 P = mk3(g1.x, g1.y, g1.z), d = P - pos, nrm = cross(right, up);
+        const f3 d = P - pos, nrm = cross(right, up);
         const float num = dot(nrm, p1 - pos), den = dot(nrm, d);
         if (num * den > 0.0f) { // (else behind the previous camera)
             const f3 q = pos + (num / den) * d - p1;
@@ -241,10 +352,11 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal(const CameraP
                         const uint32_t k = (uint32_t)qx + (uint32_t)qy * cam.width;
                         const float4 xq = tp.prev[k];
                         if (!(xq.w > 0.0f)) continue;
+                        if (MOTION && mp.prev_ids[k] != id) continue;
                         const float4 g0q = tp.prev[plane + k], g1q = tp.prev[2u * plane + k];
-                        float wn = gl_max(0.0f, g0.x * g0q.x + g0.y * g0q.y + g0.z * g0q.z);
+                        float wn = gl_max(0.0f, N.x * g0q.x + N.y * g0q.y + N.z * g0q.z);
                         for (int r = 0; r < kDnNormalSquarings; r++) wn = wn * wn;
-                        const float dp = g0.x * (g1q.x - g1.x) + g0.y * (g1q.y - g1.y) + g0.z * (g1q.z - g1.z);
+                        const float dp = N.x * (g1q.x - P.x) + N.y * (g1q.y - P.y) + N.z * (g1q.z - P.z);
                         const float wp = gl_max(0.0f, 1.0f - gl_abs(dp) * inv_plane);
                         const float w = (e ? tx : 1.0f - tx) * (b ? ty : 1.0f - ty) * wn * wp;
                         sw += w;
@@ -266,9 +378,31 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal(const CameraP
     tp.cur[i] = make_float4(x.x, x.y, x.z, h);
 }
 
+__global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal(const CameraParams cam, const DnTemporalParams tp)
+{
+    dn_temporal_pixel<false>(cam, tp, DnMotionParams{});
+}
+
+__global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal_motion(const CameraParams cam, const DnTemporalParams tp, const DnMotionParams mp)
+{
+    dn_temporal_pixel<true>(cam, tp, mp);
+}
+
 void launch_dn_guide(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, float4* guide, uint32_t pixel_mask)
 {
     if (p.capacity) hipLaunchKernelGGL(k_dn_guide, dim3((p.capacity + 255u) / 256u), dim3(256), 0, s, cam, sc, p, guide, pixel_mask);
+}
+
+void launch_dn_ids(hipStream_t s, const CameraParams& cam, const PathDev& p, uint32_t* ids, uint32_t pixel_mask)
+{
+    if (p.capacity) hipLaunchKernelGGL(k_dn_ids, dim3((p.capacity + 255u) / 256u), dim3(256), 0, s, cam, p, ids, pixel_mask);
+}
+
+void launch_dn_motion(hipStream_t s, const rfw_mat4* matrices, const InstanceXform* xf, const InstanceNormal* nm, uint32_t n, const void* prev, uint32_t n_prev,
+                      void* cur, void* records)
+{
+    if (n) hipLaunchKernelGGL(k_dn_motion, dim3((n + 63u) / 64u), dim3(64), 0, s, matrices, xf, nm, n, static_cast<const DnInstance*>(prev), n_prev,
+                              static_cast<DnInstance*>(cur), static_cast<DnMotion*>(records));
 }
 
 template <bool TILED> static void launch_atrous_pass(hipStream_t s, const CameraParams& cam, const DnParams& dp, bool first, bool last)
@@ -285,7 +419,7 @@ template <bool TILED> static void launch_atrous_pass(hipStream_t s, const Camera
 }
 
 void launch_dn_temporal(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, const float4* prev, float4* cur,
-                        const float prev_view[12], uint32_t samples, uint32_t max_history)
+                        const float prev_view[12], uint32_t samples, uint32_t max_history, const DnMotionLaunch* motion)
 {
     DnTemporalParams tp;
     tp.acc = acc;
@@ -296,7 +430,18 @@ void launch_dn_temporal(hipStream_t s, const CameraParams& cam, const float4* ac
     for (int k = 0; k < 3; k++) { tp.pos[k] = prev_view[k]; tp.p1[k] = prev_view[3 + k]; tp.right[k] = prev_view[6 + k]; tp.up[k] = prev_view[9 + k]; }
     tp.samples = samples;
     tp.max_history = (float)max_history;
-    hipLaunchKernelGGL(k_dn_temporal, dim3(ceil_div(cam.width, kDnTile), ceil_div(cam.height, kDnTile)), dim3(kDnTile * kDnTile), 0, s, cam, tp);
+    const dim3 grid(ceil_div(cam.width, kDnTile), ceil_div(cam.height, kDnTile)), block(kDnTile * kDnTile);
+    if (motion == nullptr) {
+        hipLaunchKernelGGL(k_dn_temporal, grid, block, 0, s, cam, tp);
+        return;
+    }
+    DnMotionParams mp;
+    mp.ids = motion->ids;
+    mp.prev_ids = motion->prev_ids;
+    mp.cur_ids = motion->cur_ids;
+    mp.records = static_cast<const DnMotion*>(motion->records);
+    mp.n_records = motion->n_records;
+    hipLaunchKernelGGL(k_dn_temporal_motion, grid, block, 0, s, cam, tp, mp);
 }
 
 void launch_atrous(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, float4* const planes[2], float4* frame,

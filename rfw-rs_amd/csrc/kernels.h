@@ -123,7 +123,23 @@ void launch_atrous(hipStream_t s, const CameraParams& cam, const float4* acc, ui
 // prev = the previous image's (null: none) and prev_view = pos, p1, right, up of the frame that wrote it; max_history = Hmax, in samples.
 constexpr uint32_t kDenoiseMaxHistory = 64;
 void launch_dn_temporal(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, const float4* prev, float4* cur,
-                        const float prev_view[12], uint32_t samples, uint32_t max_history);
+                        const float prev_view[12], uint32_t samples, uint32_t max_history, const struct DnMotionLaunch* motion = nullptr);
+// option "denoise_motion" (denoise.inc, DESIGN.md "Denoiser: motion").  Ids: where launch_dn_guide is, one uint32 per frame pixel, the instance
+// id of the primary hit (0xffffffff: a miss).  Motion: one thread per instance of the frame's TLAS — its entry of the snapshot `cur`
+// (kDnInstanceBytes each) that travels with the history this image writes, and its record (kDnMotionBytes: rows of A, rows of B, the state's
+// bits in the fourth float of B's first row) against the snapshot `prev` of n_prev instances (null: no history).  launch_dn_temporal with
+// `motion` runs k_dn_temporal_motion: it reads the records and both id planes and copies the frame's ids into cur_ids.
+constexpr size_t kDnInstanceBytes = 128, kDnMotionBytes = 96;
+struct DnMotionLaunch {
+    const uint32_t* ids;
+    const uint32_t* prev_ids;
+    uint32_t* cur_ids;
+    const void* records;
+    uint32_t n_records;
+};
+void launch_dn_ids(hipStream_t s, const CameraParams& cam, const PathDev& p, uint32_t* ids, uint32_t pixel_mask);
+void launch_dn_motion(hipStream_t s, const rfw_mat4* matrices, const InstanceXform* xf, const InstanceNormal* nm, uint32_t n, const void* prev, uint32_t n_prev,
+                      void* cur, void* records);
 void launch_eval_shading(hipStream_t s, const SceneDev& sc, const CameraParams& cam, int op, uint32_t n, const float* in, float* out);
 void launch_query_closest(hipStream_t s, const SceneDev& sc, const float* origins, const float* directions, float t_min, float t_max, uint64_t n,
                           rfw_hip_hit* hits, uint32_t* depth = nullptr /* optional: nodes visited per ray */);

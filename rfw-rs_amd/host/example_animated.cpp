@@ -8,13 +8,17 @@
 // Where the reference presents to a window, this program downloads the presented (Bgra8UnormSrgb) frame of every frame into a ring of
 // pinned host buffers without stalling the frames in flight, and writes the last one as a PPM image.
 //
-//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--out last.ppm]
+//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--out last.ppm]
+//
+// --denoise K (off by default) finalises every frame with K a-trous passes and a history of 16 samples that follows the bouncing
+// instances (options "denoise", "denoise_temporal", "denoise_motion"): every frame here is a new image of one sample per pixel.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rfw_host.hpp"
@@ -23,7 +27,7 @@ int main(int argc, char** argv)
 {
     std::string gltf, out = "example_animated.ppm";
     std::vector<std::string> actors;
-    uint32_t frames = 240, width = 1280, height = 720, nx = 100, nz = 100, path_length = 2;
+    uint32_t frames = 240, width = 1280, height = 720, nx = 100, nz = 100, path_length = 2, denoise = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -33,6 +37,7 @@ int main(int argc, char** argv)
         else if (a == "--size") std::sscanf(next(), "%ux%u", &width, &height);
         else if (a == "--spheres") std::sscanf(next(), "%ux%u", &nx, &nz);
         else if (a == "--path-length") path_length = (uint32_t)std::atoi(next());
+        else if (a == "--denoise") denoise = (uint32_t)std::atoi(next());
         else if (a == "--out") out = next();
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -69,6 +74,10 @@ int main(int argc, char** argv)
         opt.world = 1;
         opt.frames_in_flight = 4; // one HIP stream per frame slot
         std::unique_ptr<rfw::HipBackend> renderer(rfw::HipBackend::init(width, height, 1.0, &opt));
+
+        if (denoise)
+            for (const auto& kv : {std::pair<const char*, double>{"denoise", (double)denoise}, {"denoise_temporal", 16.0}, {"denoise_motion", 1.0}})
+                if (rfw_hip_set_option(renderer->raw(), kv.first, kv.second) != RFW_HIP_OK) throw std::runtime_error(rfw_hip_last_error(renderer->raw()));
 
         const uint64_t px = (uint64_t)width * height;
         std::vector<uint32_t*> ring(8, nullptr); // presented frames land here, 8 frames of slack

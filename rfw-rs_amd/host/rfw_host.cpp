@@ -1529,6 +1529,17 @@ HOST_API int rfwhost_instance_matrix(void* p, uint32_t mesh, uint32_t slot, floa
     std::memcpy(out16, &it->second.matrices[slot], 16 * sizeof(float));
     return it->second.skin_ids.size() > slot ? it->second.skin_ids[slot] + 1 : 0; // 0: unskinned, else skin id + 1
 }
+// Scene::set_matrix: the matrix (16 floats, column-major) of instance `slot` of mesh `mesh`, marked changed for the next synchronize; -1: no such slot
+HOST_API int rfwhost_set_instance_matrix(void* p, uint32_t mesh, uint32_t slot, const float* m16)
+{
+    HostScene& h = *(HostScene*)p;
+    auto it = h.scene.instances_3d.find(mesh);
+    if (it == h.scene.instances_3d.end() || slot >= it->second.matrices.size() || !m16) return -1;
+    rfw_mat4 m;
+    std::memcpy(&m, m16, 16 * sizeof(float));
+    h.scene.set_matrix(mesh, slot, m);
+    return 0;
+}
 // PNG or JPEG bytes -> RGBA8; returns 0 and the size, -1 with the reason in *err_out (static storage, valid until the next call on this thread)
 HOST_API int rfwhost_decode_image(const uint8_t* data, uint64_t n, uint32_t* w, uint32_t* hgt, uint8_t* rgba_out, uint64_t cap, const char** err_out)
 {

@@ -59,6 +59,7 @@ def host_lib():
         l.rfwhost_animation_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
         l.rfwhost_skin_matrices.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint32]
         l.rfwhost_instance_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        l.rfwhost_set_instance_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         l.rfwhost_decode_image.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p)]
         _lib = l
     return _lib
@@ -204,6 +205,14 @@ class Scene:
         if rc < 0:
             raise KeyError((mesh, slot))
         return out.reshape(4, 4).T, rc - 1                # (matrix, skin id or -1)
+
+    def set_instance_matrix(self, mesh, slot, matrix):
+        """Scene::set_matrix: `matrix` ([row, column], as instance_matrix() returns it) becomes the matrix of instance `slot` of mesh `mesh`,
+        marked changed for the next sync()."""
+        import numpy as np
+        m = np.ascontiguousarray(np.asarray(matrix, np.float32).reshape(4, 4).T)  # column-major storage
+        if self._l.rfwhost_set_instance_matrix(self._h, mesh, slot, m.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+            raise KeyError((mesh, slot))
 
     def set_camera(self, pos, direction, fov=40.0, aperture=0.0, aspect=1.0):
         p = (C.c_float * 3)(*pos)
