@@ -32,6 +32,8 @@ extern "C" {
     fn rfw_hip_create(width: u32, height: u32, scale: c_double, options: *const Options) -> *mut c_void;
     fn rfw_hip_destroy(instance: *mut c_void);
     fn rfw_hip_last_error(instance: *mut c_void) -> *const c_char;
+    fn rfw_hip_set_2d_mesh(instance: *mut c_void, id: u32, vertices: *const Vertex2D, num_vertices: u32, tex_id: i32) -> c_int;
+    fn rfw_hip_set_2d_instances(instance: *mut c_void, mesh: u32, matrices: *const Mat4, num_matrices: u32) -> c_int;
     fn rfw_hip_set_3d_mesh(instance: *mut c_void, id: u32, data: *const MeshData3DC) -> c_int;
     fn rfw_hip_unload_3d_meshes(instance: *mut c_void, ids: *const u32, n: u32) -> c_int;
     fn rfw_hip_set_3d_instances(instance: *mut c_void, mesh: u32, data: *const InstancesData3DC) -> c_int;
@@ -108,8 +110,15 @@ impl FromWindowHandle for HipBackend {
 }
 
 impl Backend for HipBackend {
-    fn set_2d_mesh(&mut self, _id: usize, _data: MeshData2D<'_>) {}
-    fn set_2d_instances(&mut self, _mesh: usize, _instances: InstancesData2D<'_>) {}
+    // the 2D layer (DESIGN.md "2D layer"): the slices are copied before the call returns and drawn over every frame rendered after the next
+    // synchronize(); the mesh's tex_id decides whether it is textured (the per-vertex `tex` is not read)
+    fn set_2d_mesh(&mut self, id: usize, data: MeshData2D<'_>) {
+        let tex_id = data.tex_id.map(|t| t as i32).unwrap_or(-1);
+        self.check(unsafe { rfw_hip_set_2d_mesh(self.instance, id as u32, data.vertices.as_ptr(), data.vertices.len() as u32, tex_id) });
+    }
+    fn set_2d_instances(&mut self, mesh: usize, instances: InstancesData2D<'_>) {
+        self.check(unsafe { rfw_hip_set_2d_instances(self.instance, mesh as u32, instances.matrices.as_ptr(), instances.matrices.len() as u32) });
+    }
 
     fn set_3d_mesh(&mut self, id: usize, data: MeshData3D<'_>) {
         let d = MeshData3DC { vertices: data.vertices.as_ptr(), num_vertices: data.vertices.len() as u32,
@@ -196,5 +205,13 @@ mod tests {
         assert_eq!(std::mem::size_of::<VertexMesh>(), 48);
         assert_eq!(std::mem::size_of::<JointData>(), 32);
         assert_eq!(std::mem::size_of::<Mat4>(), 64);
+        // rfw_vertex_2d of include/rfw_pod.h: vertex at 0, tex at 12, uv at 16, color at 24
+        assert_eq!(std::mem::size_of::<Vertex2D>(), 40);
+        let v = Vertex2D { vertex: [0.0; 3], tex: 0, uv: [0.0; 2], color: [0.0; 4] };
+        let base = &v as *const Vertex2D as usize;
+        assert_eq!(&v.vertex as *const _ as usize - base, 0);
+        assert_eq!(&v.tex as *const _ as usize - base, 12);
+        assert_eq!(&v.uv as *const _ as usize - base, 16);
+        assert_eq!(&v.color as *const _ as usize - base, 24);
     }
 }

@@ -165,8 +165,27 @@ RFW_HIP_API uint32_t rfw_hip_selftest_index_magic(uint32_t d, uint64_t n_max);
 RFW_HIP_API int64_t rfw_hip_selftest_bvh(const float* boxes6, uint32_t n, uint32_t max_leaf, uint32_t threads, uint32_t* out_nodes);
 
 /* ---- Backend trait, in declaration order (crates/rfw-backend/src/lib.rs:36-81) ---- */
-/* :36 set_2d_mesh / :39 set_2d_instances — accepted and ignored; gpu-rt `unimplemented!()`s them
- * (backends/gpu-rt/src/lib.rs:1131-1137). */
+/* :36 set_2d_mesh / :39 set_2d_instances — the 2D layer (DESIGN.md "2D layer"): text, HUDs, UI drawn over the finished frame, as the
+ * reference's wgpu backend draws them (gpu-rt itself `unimplemented!()`s both, backends/gpu-rt/src/lib.rs:1131-1137).
+ * set_2d_mesh: `vertices` = num_vertices records of rfw_vertex_2d (rfw_pod.h; the trait's Vertex2D, 40 bytes), a triangle list (a trailing
+ * num_vertices % 3 is ignored); NULL / 0 empties the mesh.  tex_id >= 0: texture tex_id of set_textures, sampled at level 0 as the device
+ * stores it (bilinear, repeat) and multiplied with the vertex colour; < 0: untextured.  The per-vertex `tex` is NOT read (the reference
+ * reads tex == 0 as "no texture", which makes texture 0 unusable): the mesh's tex_id decides.  A mesh whose tex_id is at or beyond the
+ * texture count when a frame is drawn is not drawn.
+ * set_2d_instances: column-major matrices replace the mesh's instance list; 0 removes it.  A zero matrix (the trait's removed slot) draws
+ * nothing.
+ * Both copy before they return; the data reaches the device in rfw_hip_synchronize(), as a new version of two small arrays: a frame shows
+ * the 2D state of the last synchronize() before its render(), an edit never waits for frames in flight and never changes a frame already
+ * submitted.  Triangles x instances over all 2D meshes: at most 2^20 per frame, else synchronize() fails with RFW_HIP_E_INVALID
+ * before it touches anything; the refused 2D state stays pending, so every later synchronize() fails the same way until the caller has
+ * shrunk the meshes or their instance lists.  A mesh without vertices and without instances is forgotten.
+ * Draw order: meshes by ascending id, instances by ascending index, triangles by ascending index; later ones over earlier ones; z is not
+ * compared.  Per triangle: clip = view_2d * (M * (v, 1)); dropped when a w <= 0, a component is not finite or |pixel| > 16384 (no
+ * clipping); pixel = ((x / w * 0.5 + 0.5) * W, (0.5 - 0.5 * y / w) * H), row 0 at the top, snapped to 8 sub-pixel bits; coverage is exact
+ * integer arithmetic at the pixel centres with the top-left rule (two triangles that share an edge cover every pixel along it once; both
+ * windings are drawn); uv and colour are interpolated affinely in screen space.  Per covered pixel, a = src.a: not finite or <= 0: skipped;
+ * >= 1: dst.rgb = src.rgb; else dst.rgb = a src.rgb + (1 - a) dst.rgb.  dst.w is never touched.  Colours are in the space of the
+ * finalised frame (what rfw_hip_read_framebuffer returns and the presented frame encodes). */
 RFW_HIP_API int rfw_hip_set_2d_mesh(void* instance, uint32_t id, const void* vertices, uint32_t num_vertices, int32_t tex_id);
 RFW_HIP_API int rfw_hip_set_2d_instances(void* instance, uint32_t mesh, const rfw_mat4* matrices, uint32_t num_matrices);
 /* :41 set_3d_mesh */
@@ -233,6 +252,12 @@ enum {
     RFW_HIP_RENDER_SSAO = 5,
     RFW_HIP_RENDER_FILTERED_SSAO = 6
 };
+/* view_2d: the frame's CameraView2D::matrix.  The 2D meshes are drawn over the finalised frame, in place (it shows in
+ * rfw_hip_read_framebuffer* and rfw_hip_download_frame what = 0 and 2; never in the accumulator, the denoiser's guide, planes or history),
+ * in every mode, on every frame slot, with sub-streams — where the frame is de-tiled on this device: world <= 1 and no communicator,
+ * loop-back hub, peer exchange or external slab.  A sharded or exchanged frame is finalised without the 2D layer, as mode 6's filter and
+ * option "denoise" are skipped there; rfw_hip_render_batch and rfw_hip_render_samples take no view_2d and draw none.  NULL: no 2D layer
+ * this frame.  With no 2D instance whose mesh has triangles, or with NULL, no extra launch is issued and nothing is allocated. */
 RFW_HIP_API int rfw_hip_render(void* instance, const rfw_mat4* view_2d, const rfw_camera_view_3d* view_3d, uint32_t mode);
 /* :63 resize */
 RFW_HIP_API int rfw_hip_resize(void* instance, uint32_t width, uint32_t height, double scale);
@@ -380,7 +405,12 @@ RFW_HIP_API int rfw_hip_occludes4(void* instance, const float* origin_xyz4, cons
  * "dn_motion" (option "denoise_motion"): the records the latest temporal frame used, one of 96 bytes per instance id of that frame: the
  * rows of A = M' inverse(M) (3 x 4 floats: a point of this image -> the same point of the instance in the previous image), then the rows
  * of B = transpose(inverse(A)) (3 x 4 floats, of which [0][3] holds the uint32 state — 0 no history, 1 the matrix did not change, 2 moved —
- * and [1][3], [2][3] are 0).  A and B are zero where the state is 0. */
+ * and [1][3], [2][3] are 0).  A and B are zero where the state is 0.
+ * "ov_prims" (the 2D layer): one record of 48 bytes per primitive of the latest frame's 2D layer, in draw order: int32 X[3], Y[3] (the
+ * snapped vertices, 8 sub-pixel bits, in the caller's vertex order; 0 where a vertex had no pixel position: w <= 0, not finite, too far), uint32 mesh, instance, triangle,
+ * dropped (0 or 1), two pad words; nothing when the latest frame drew no 2D layer.  "ov_stats": three uint32 of that frame: primitives
+ * drawn, primitives dropped, bin words written.  With frame slots both taps follow the slot of the latest frame, like the other per-frame
+ * taps. */
 RFW_HIP_API int rfw_hip_debug_read(void* instance, const char* what, void* dst, uint64_t bytes, uint64_t* written);
 
 /* occludes() that also reports how many 4-wide nodes each any-hit traversal visited (the any-hit counterpart of rfw_hip_depth_test).  For

@@ -161,6 +161,14 @@ enum {
     RFW_MAT_HAS_METALLIC_MAP = 1u << 3, RFW_MAT_HAS_EMISSIVE_MAP = 1u << 4, RFW_MAT_HAS_SHEEN_MAP = 1u << 5
 };
 
+/* rfw_backend::Vertex2D (the vertices of set_2d_mesh): a triangle list; `tex` is ignored here, the mesh's tex_id decides */
+typedef struct {
+    float vertex[3];
+    uint32_t tex;
+    float uv[2];
+    float color[4];
+} rfw_vertex_2d;
+
 /* ---- borrowed-slice payloads (Rust `MeshData3D<'a>` etc. lowered to pointer + count) ---- */
 
 /* crates/rfw-backend/src/structs.rs:332-341; C shape follows backends/metal/cpp/src/library.h:62-73 */
@@ -204,6 +212,8 @@ RFW_STATIC_ASSERT(offsetof(rfw_rt_triangle, normal) == 48 && offsetof(rfw_rt_tri
 RFW_STATIC_ASSERT(offsetof(rfw_rt_triangle, id) == 108 && offsetof(rfw_rt_triangle, tangent0) == 112, "RTTriangle tangents");
 RFW_STATIC_ASSERT(offsetof(rfw_rt_triangle, light_id) == 160 && offsetof(rfw_rt_triangle, area) == 172, "RTTriangle tail");
 RFW_STATIC_ASSERT(sizeof(rfw_vertex_3d) == 64 && offsetof(rfw_vertex_3d, tangent) == 48, "Vertex3D");
+RFW_STATIC_ASSERT(sizeof(rfw_vertex_2d) == 40 && offsetof(rfw_vertex_2d, tex) == 12, "Vertex2D");
+RFW_STATIC_ASSERT(offsetof(rfw_vertex_2d, uv) == 16 && offsetof(rfw_vertex_2d, color) == 24, "Vertex2D attributes");
 RFW_STATIC_ASSERT(sizeof(rfw_joint_data) == 32, "JointData");
 RFW_STATIC_ASSERT(sizeof(rfw_vertex_mesh) == 48, "VertexMesh");
 RFW_STATIC_ASSERT(sizeof(rfw_device_material) == 96 && offsetof(rfw_device_material, flags) == 64, "DeviceMaterial");

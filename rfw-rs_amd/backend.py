@@ -133,6 +133,23 @@ def hip_lib():
 HIT_DTYPE = np.dtype([("inst", "<i4"), ("tri", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4")])
 
 
+VERTEX_2D = np.dtype([("vertex", "<f4", 3), ("tex", "<u4"), ("uv", "<f4", 2), ("color", "<f4", 4)])  # pod.Vertex2D
+OVERLAY_PRIM = np.dtype([("X", "<i4", 3), ("Y", "<i4", 3), ("mesh", "<u4"), ("instance", "<u4"), ("triangle", "<u4"), ("dropped", "<u4"), ("pad", "<u4", 2)])
+
+
+def vertices_2d(vertices):
+    """(n,) VERTEX_2D records from such records or from an (n, 10) float array of x, y, z, unused, u, v, r, g, b, a (the column in the place of `tex` is dropped: `tex` = 0)."""
+    if vertices is None:
+        return np.zeros(0, VERTEX_2D)
+    a = np.asarray(vertices)
+    if a.dtype == VERTEX_2D:
+        return np.ascontiguousarray(a).reshape(-1)
+    a = np.asarray(a, dtype=np.float32).reshape(-1, 10)
+    v = np.zeros(len(a), VERTEX_2D)
+    v["vertex"], v["uv"], v["color"] = a[:, 0:3], a[:, 4:6], a[:, 6:10]
+    return v
+
+
 class BackendError(RuntimeError):
     pass
 
@@ -193,16 +210,28 @@ class HipBackend:
         t = BackendTable()
         t.instance = self._h
         for name in ("set_3d_mesh", "unload_3d_meshes", "set_3d_instances", "set_materials", "synchronize",
-                     "set_point_lights", "set_spot_lights", "set_area_lights", "set_directional_lights", "set_textures", "set_skybox", "set_skins"):
+                     "set_point_lights", "set_spot_lights", "set_area_lights", "set_directional_lights", "set_textures", "set_skybox", "set_skins",
+                     "set_2d_mesh", "set_2d_instances"):
             setattr(t, name, C.cast(getattr(self._l, "rfw_hip_" + name), C.c_void_p))
         return t
 
     # ---- trait methods (same order as the trait) ----
-    def set_2d_mesh(self, id, data=None):
-        self._check(self._l.rfw_hip_set_2d_mesh(self._h, id, None, 0, -1))
+    def set_2d_mesh(self, id, vertices=None, tex_id=None):
+        """vertices: (n,) VERTEX_2D records or an (n, 10) float array (x, y, z, unused, u, v, r, g, b, a), a triangle list; None or empty: the
+        mesh is emptied.  tex_id: the texture of set_textures the mesh is drawn with, None: untextured."""
+        v = vertices_2d(vertices)
+        self._check(self._l.rfw_hip_set_2d_mesh(self._h, id, v.ctypes.data if len(v) else None, len(v), -1 if tex_id is None else int(tex_id)))
 
-    def set_2d_instances(self, mesh, instances=None):
-        self._check(self._l.rfw_hip_set_2d_instances(self._h, mesh, None, 0))
+    def set_2d_instances(self, mesh, matrices=None):
+        """matrices: (n, 4, 4) or (n, 16) column-major Mat4s (numpy: m[k] is what glam's to_cols_array gives), or pod.Mat4s; None: no instance."""
+        if matrices is None or len(matrices) == 0:
+            self._check(self._l.rfw_hip_set_2d_instances(self._h, mesh, None, 0))
+            return
+        if isinstance(matrices[0], pod.Mat4):
+            m = np.array([list(x.m) for x in matrices], dtype=np.float32)
+        else:
+            m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 16)
+        self._check(self._l.rfw_hip_set_2d_instances(self._h, mesh, m.ctypes.data, len(m)))
 
     def set_3d_mesh(self, id, data):
         self._check(self._l.rfw_hip_set_3d_mesh(self._h, id, C.byref(data)))
@@ -232,7 +261,12 @@ class HipBackend:
         self._check(self._l.rfw_hip_synchronize(self._h))
 
     def render(self, view_3d, view_2d=None, mode=0):
-        self._check(self._l.rfw_hip_render(self._h, None, C.byref(view_3d), int(mode)))  # RenderMode, or any int (unknown values render DEFAULT)
+        """view_2d: the frame's CameraView2D matrix (pod.Mat4 or 16 column-major floats); None: no 2D layer over this frame."""
+        m = None
+        if view_2d is not None:
+            m = view_2d if isinstance(view_2d, pod.Mat4) else pod.Mat4((C.c_float * 16)(*np.asarray(view_2d, dtype=np.float32).reshape(16)))
+            m = C.byref(m)
+        self._check(self._l.rfw_hip_render(self._h, m, C.byref(view_3d), int(mode)))  # RenderMode, or any int (unknown values render DEFAULT)
 
     def resize(self, window_size, scale_factor=1.0):
         self._check(self._l.rfw_hip_resize(self._h, window_size[0], window_size[1], scale_factor))
@@ -502,6 +536,18 @@ class HipBackend:
         w = C.c_uint64(0)
         self._check(self._l.rfw_hip_debug_read(self._h, what.encode(), buf.ctypes.data, nbytes, C.byref(w)))
         return buf[: int(w.value)]
+
+    def overlay_prims(self):
+        """The 2D layer's primitives of the latest frame in draw order (OVERLAY_PRIM records): the snapped vertices (8 sub-pixel bits, the
+        caller's vertex order), mesh id, instance index, triangle index and the dropped flag; empty when the frame drew no 2D layer."""
+        st = self.overlay_stats()
+        raw = self.debug_read("ov_prims", 48 * (st["drawn"] + st["dropped"])).tobytes()
+        return np.frombuffer(raw, OVERLAY_PRIM).copy()
+
+    def overlay_stats(self):
+        """The 2D layer of the latest frame: primitives drawn, primitives dropped, bin words written."""
+        v = np.frombuffer(self.debug_read("ov_stats", 12).tobytes(), np.uint32)
+        return {"drawn": int(v[0]), "dropped": int(v[1]), "bin_words": int(v[2])}
 
     def denoise_guide(self):
         """The denoiser's guide of the latest frame (option "denoise"): g0 = (faced gN, t), g1 = (P, 0), g2 = (albedo, f), each (H, W, 4)."""

@@ -300,6 +300,22 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         for (int q = 0; q < 2; q++) HIP_TRY(I, O->d_dn_history_ids[q].ensure(px));
     }
 
+    // The 2D layer: where the frame is de-tiled on this device and the call leaves one image of rfw_hip_render behind, the draws of the last
+    // synchronize() go over the finalised frame.  Nothing to draw, or no view_2d: no launch, no allocation, no wait.
+    const Instance::OvVersion* ov = nullptr;
+    I->ov_frame_prims = I->ov_frame_words = 0;
+    if (O->view_2d && k == 1 && !samples && I->world <= 1 && !O->comm && !O->loop && !O->p2p.connected && !I->external_slab) {
+        const Instance::OvVersion& v = O->ov[O->ov_version % Instance::kTableVersions];
+        if (v.n_prims) {
+            ov = &v;
+            if (I->ov_waited != O->ov_version) {
+                HIP_TRY(I, hipStreamWaitEvent(main, O->ov_ready, 0));
+                I->ov_waited = O->ov_version;
+            }
+            if (I->ov_oldest_pending == ~0ull) I->ov_oldest_pending = O->ov_version;
+        }
+    }
+
     if (tm) (void)hipEventRecord(I->events[EV_FRAME0], main);
     // queue counters: this frame takes the block the previous frame's k_primary cleared (alloc_paths cleared both), and clears the other
     I->counter_phase ^= 1u;
@@ -484,6 +500,23 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         else if (mode == RFW_HIP_RENDER_FILTERED_SSAO) launch_ao_filter(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_ao_guide.ptr, I->d_frame_out.ptr, I->sample_count);
         else launch_assemble(main, cam[0], I->d_acc_slab.ptr, false, false, I->cap_v, I->d_frame_out.ptr, I->sample_count, mode != RFW_HIP_RENDER_DEFAULT);
         I->acc_source = I->d_acc_slab.ptr; I->acc_source_rgb = false; I->acc_source_batch = frames_out;
+        if (ov) { // the 2D layer, in place over the frame the finaliser just wrote (behind the history's event: the history never sees it)
+            const uint32_t n = ov->n_prims;
+            OvFrame f;
+            std::memcpy(f.view, O->view_2d->m, sizeof(f.view));
+            f.width = I->width; f.height = I->height;
+            f.n_prims = n; f.n_draws = ov->n_draws; f.n_textures = O->n_textures;
+            f.bins_x = (I->width + kOvBin - 1u) / kOvBin; f.bins_y = (I->height + kOvBin - 1u) / kOvBin;
+            f.chunks = (n + 63u) / 64u;
+            const size_t n_words = (size_t)f.bins_x * f.bins_y * f.chunks;
+            HIP_TRY(I, I->d_ov_prims.ensure(n));
+            HIP_TRY(I, I->d_ov_tap.ensure(n));
+            HIP_TRY(I, I->d_ov_words.ensure(n_words));
+            launch_overlay(main, f, ov->vertices.ptr, ov->draws.ptr, I->d_ov_prims.ptr, I->d_ov_tap.ptr, I->d_ov_words.ptr, O->d_tex_data.ptr, O->d_tex_desc.ptr,
+                           I->d_frame_out.ptr);
+            I->ov_frame_prims = n;
+            I->ov_frame_words = (uint32_t)n_words;
+        }
     }
     if (I->external_slab) // this rank's contribution to the all-gather, [frame][sub-shard][slot] in the instance's gather format
         pack_slabs(I, main, I->external_slab, frames_out);
@@ -694,6 +727,7 @@ void rfw_hip_destroy(void* inst)
         I->d_dn_ids.release(); I->d_dn_motion.release();
         for (int q = 0; q < 2; q++) { I->d_dn_history_ids[q].release(); I->d_dn_snapshot[q].release(); }
         if (I->dn_chain) (void)hipEventDestroy(I->dn_chain);
+        release_overlay(I);
         for (auto& ev : I->ring)
             if (ev) (void)hipEventDestroy(ev);
         if (I->ev_fork) (void)hipEventDestroy(I->ev_fork);
@@ -740,13 +774,16 @@ static int render_impl(Instance* I, const rfw_camera_view_3d* views, uint32_t k,
     return rc;
 }
 
-int rfw_hip_render(void* inst, const rfw_mat4* /*view_2d*/, const rfw_camera_view_3d* view, uint32_t mode)
+int rfw_hip_render(void* inst, const rfw_mat4* view_2d, const rfw_camera_view_3d* view, uint32_t mode)
 {
     LOCK(inst);
     if (!view) return fail(I, RFW_HIP_E_INVALID, "render: null view");
     CHECK_OVERFLOW(I); // of an earlier frame or query (sticky until synchronize() rebuilds the trees)
     // unknown values render as DEFAULT (the wgpu backend shows its default output for them too)
-    return render_impl(I, view, 1, false, mode <= (uint32_t)RFW_HIP_RENDER_FILTERED_SSAO ? mode : (uint32_t)RFW_HIP_RENDER_DEFAULT);
+    I->view_2d = view_2d; // (read by do_render, whichever slot runs the frame)
+    const int rc = render_impl(I, view, 1, false, mode <= (uint32_t)RFW_HIP_RENDER_FILTERED_SSAO ? mode : (uint32_t)RFW_HIP_RENDER_DEFAULT);
+    I->view_2d = nullptr;
+    return rc;
 }
 
 int rfw_hip_render_batch(void* inst, const rfw_camera_view_3d* views, uint32_t count)
@@ -795,6 +832,7 @@ int rfw_hip_resize(void* inst, uint32_t w, uint32_t h, double)
     I->d_dn_ids.release(); I->d_dn_motion.release();
     for (int q = 0; q < 2; q++) { I->d_dn_history_ids[q].release(); I->d_dn_snapshot[q].release(); I->dn_snap_count[q] = 0; }
     I->dn_motion_count = 0;
+    I->ov_frame_prims = I->ov_frame_words = 0; // the 2D layer's taps describe a frame of the old size
     // a gathered frame not de-tiled yet belongs to the old size (and d_recv may move below): forget it (each slot passes here for itself)
     I->deferred = Instance::Deferred(); I->acc_source = nullptr; I->presented_valid = false;
     const int arc = alloc_paths(I); // also restarts accumulation (gpu-rt/src/lib.rs:1809)

@@ -506,6 +506,27 @@ struct Instance {
     DevBuf<uint32_t> d_dn_history_ids[2];
     DevBuf<char> d_dn_snapshot[2], d_dn_motion;
     uint32_t dn_snap_count[2] = {}, dn_motion_count = 0;
+    // The 2D layer (DESIGN.md "2D layer").  Owner: the host copies of set_2d_mesh / set_2d_instances; synchronize() flattens them into the
+    // draws of a frame (mesh id, then instance index) and writes them as a NEW version of two small device arrays on the upload stream, the
+    // way the material and light tables are versioned: frames in flight keep the version they started with and nothing waits for them.
+    // Per slot: the records, tap and bin words of its latest overlay frame, allocated at the first frame that draws something.
+    struct Mesh2D { std::vector<rfw_vertex_2d> vertices; int32_t tex = -1; std::vector<rfw_mat4> matrices; };
+    std::map<uint32_t, Mesh2D> meshes_2d;
+    bool ov_dirty = false;
+    struct OvVersion {
+        DevBuf<rfw_vertex_2d> vertices;
+        DevBuf<OvDraw> draws;
+        uint32_t n_draws = 0, n_prims = 0;
+    } ov[kTableVersions];
+    uint64_t ov_version = 0;                 // owner: version frames rendered from now on draw
+    uint64_t ov_waited = 0;                  // per slot: version its stream has waited for
+    uint64_t ov_oldest_pending = ~0ull;      // per slot: as tables_oldest_pending
+    hipEvent_t ov_ready = nullptr;
+    const rfw_mat4* view_2d = nullptr;       // owner: rfw_hip_render's argument for the duration of the call
+    DevBuf<OvPrim> d_ov_prims;
+    DevBuf<OvTap> d_ov_tap;
+    DevBuf<uint64_t> d_ov_words;
+    uint32_t ov_frame_prims = 0, ov_frame_words = 0; // per slot: primitives and bin words of its latest frame (0: it drew no overlay)
     // per TLAS holder (tlas_of): the forward matrices its instance descriptors were made from — d_matrices (the launch chain) or the
     // matrices inside d_stage_dev (the fused path)
     const rfw_mat4* d_forward = nullptr;
@@ -612,6 +633,7 @@ uint32_t index_magic(uint32_t d, uint64_t n_max); // api_frame.cpp: reciprocal f
 int do_synchronize(Instance* I);
 int ensure_slot_tlas(Instance* S, Instance* T);
 int ensure_lbvh_ws(Instance* I, uint32_t n);
+void release_overlay(Instance* I);
 // api_exchange.cpp
 uint64_t slab_words(const Instance* I);
 const float* srgb_steps();

@@ -239,7 +239,7 @@ int rfw_hip_debug_lbvh_stress(void* inst, uint32_t n, uint32_t iterations, uint3
 // what: "hit0"/"hit1" (uint4), "ray_o0"/"ray_o1", "ray_d0"/"ray_d1", "thr0"/"thr1", "sh_o", "sh_d", "sh_e" (float4), "counters",
 //       "xforms" (InstanceXform), "normals" (InstanceNormal), "ao_rays", "ao_guide" (render modes 5, 6: DESIGN.md "Render modes"),
 //       "dn_guide" (option "denoise": DESIGN.md "Denoiser"), "dn_history" (option "denoise_temporal": DESIGN.md "Denoiser: temporal"),
-//       "dn_ids", "dn_motion" (option "denoise_motion": DESIGN.md "Denoiser: motion")
+//       "dn_ids", "dn_motion" (option "denoise_motion": DESIGN.md "Denoiser: motion"), "ov_prims", "ov_stats" (DESIGN.md "2D layer")
 int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, uint64_t* written)
 {
     LOCK(inst);
@@ -311,6 +311,18 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
         if (written) *written = n;
         return RFW_HIP_OK;
     }
+    if (w == "ov_stats") { // the 2D layer of the latest frame: primitives drawn, primitives dropped, bin words written
+        HIP_TRY(I, hipStreamSynchronize(I->stream));
+        const uint32_t np = (uint32_t)std::min<size_t>(I->ov_frame_prims, I->d_ov_tap.cap);
+        std::vector<OvTap> tap(np);
+        if (np) HIP_TRY(I, hipMemcpy(tap.data(), I->d_ov_tap.ptr, (size_t)np * sizeof(OvTap), hipMemcpyDeviceToHost));
+        uint32_t v[3] = {0u, 0u, I->ov_frame_words};
+        for (const OvTap& t : tap) v[t.dropped ? 1 : 0]++;
+        const uint64_t n = std::min<uint64_t>(bytes, sizeof(v));
+        std::memcpy(dst, v, n);
+        if (written) *written = n;
+        return RFW_HIP_OK;
+    }
     const void* src = nullptr;
     uint64_t avail = 0;
     const uint64_t q = (uint64_t)I->capacity * 16;
@@ -328,6 +340,7 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
     else if (w == "ao_guide") { src = I->d_ao_guide.ptr; avail = (uint64_t)std::min<size_t>((size_t)I->width * I->height, I->d_ao_guide.cap) * 16; } // (faced gN, t) per frame pixel of the latest AO frame; t = 0: the camera ray missed
     else if (w == "dn_guide") { src = I->d_dn_guide.ptr; avail = (uint64_t)std::min<size_t>((size_t)I->width * I->height * 3, I->d_dn_guide.cap) * 16; } // option "denoise": (faced gN, t), (P, 0), (albedo, f) of the latest denoised frame, plane after plane of frame pixels
     else if (w == "dn_ids") { src = I->d_dn_ids.ptr; avail = (uint64_t)std::min<size_t>((size_t)I->width * I->height, I->d_dn_ids.cap) * 4; } // option "denoise_motion": the instance id of the latest sample's primary hit per frame pixel
+    else if (w == "ov_prims") { src = I->d_ov_tap.ptr; avail = (uint64_t)std::min<size_t>(I->ov_frame_prims, I->d_ov_tap.cap) * sizeof(OvTap); } // the 2D layer: one OvTap per primitive of the latest frame, in draw order
     else if (w == "counters") { src = I->d_counters.ptr + (size_t)I->counter_phase * kMaxSub; avail = sizeof(QueueCounters); }
     else if (w == "tlas_raw") { src = I->d_tlas_raw.ptr; avail = (uint64_t)I->d_tlas_raw.cap * sizeof(Node4); }         // the device-built TLAS before quantisation (entries past the node count are stale)
     else if (w == "tlas_nodes") { src = I->d_tlas_nodes.ptr; avail = (uint64_t)I->d_tlas_nodes.cap * sizeof(Node4Q); }

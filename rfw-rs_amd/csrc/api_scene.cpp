@@ -1051,9 +1051,82 @@ int upload_tables(Instance* I)
     return RFW_HIP_OK;
 }
 
+// The 2D layer's draws of the frames to come: every (mesh, instance) pair with triangles, by mesh id, then instance index, as a new version
+// (see upload_tables for the versioning).  With nothing to draw the new version is empty and nothing is allocated or copied.
+int upload_overlay(Instance* I)
+{
+    std::vector<OvDraw> draws;
+    std::vector<rfw_vertex_2d> vertices;
+    uint64_t n_prims = 0;
+    for (const auto& kv : I->meshes_2d) {
+        const Instance::Mesh2D& m = kv.second;
+        const uint64_t n_tris = m.vertices.size() / 3;
+        if (n_tris == 0 || m.matrices.empty()) continue;
+        if (n_prims + n_tris * m.matrices.size() > kOvMaxPrims)
+            return fail(I, RFW_HIP_E_INVALID, "synchronize: the 2D meshes hold more than 2^20 triangles over all their instances");
+        const uint32_t first_vertex = (uint32_t)vertices.size();
+        vertices.insert(vertices.end(), m.vertices.begin(), m.vertices.begin() + 3 * n_tris);
+        for (size_t k = 0; k < m.matrices.size(); k++) {
+            OvDraw d;
+            std::memset(&d, 0, sizeof(d));
+            std::memcpy(d.m, m.matrices[k].m, sizeof(d.m));
+            d.first_prim = (uint32_t)n_prims;
+            d.n_tris = (uint32_t)n_tris;
+            d.first_vertex = first_vertex;
+            d.mesh = kv.first;
+            d.instance = (uint32_t)k;
+            d.tex = m.tex;
+            draws.push_back(d);
+            n_prims += n_tris;
+        }
+    }
+    const uint64_t nv = I->ov_version + 1;
+    Instance::OvVersion& dst = I->ov[nv % Instance::kTableVersions];
+    if (n_prims) {
+        if (!I->upload_stream) HIP_TRY(I, hipStreamCreateWithFlags(&I->upload_stream, hipStreamNonBlocking));
+        if (!I->ov_ready) HIP_TRY(I, hipEventCreateWithFlags(&I->ov_ready, hipEventDisableTiming));
+        if (nv >= (uint64_t)Instance::kTableVersions) { // a frame that still draws the version this buffer held has to finish first
+            const uint64_t stale = nv - Instance::kTableVersions;
+            auto order_behind = [&](Instance* c) -> int {
+                if (c->ov_oldest_pending > stale) return RFW_HIP_OK;
+                if (c->frame_done && !I->slots.empty()) HIP_TRY(I, hipStreamWaitEvent(I->upload_stream, c->frame_done, 0));
+                else HIP_TRY(I, hipStreamSynchronize(c->stream));
+                c->ov_oldest_pending = ~0ull;
+                return RFW_HIP_OK;
+            };
+            int orc;
+            if ((orc = order_behind(I))) return orc;
+            for (Instance* c : I->slots)
+                if ((orc = order_behind(c))) return orc;
+        }
+        HIP_TRY(I, dst.vertices.ensure(vertices.size()));
+        HIP_TRY(I, dst.draws.ensure(draws.size()));
+        HIP_TRY(I, I->pins.upload(dst.vertices.ptr, vertices.data(), vertices.size() * sizeof(rfw_vertex_2d), I->upload_stream));
+        HIP_TRY(I, I->pins.upload(dst.draws.ptr, draws.data(), draws.size() * sizeof(OvDraw), I->upload_stream));
+        HIP_TRY(I, hipEventRecord(I->ov_ready, I->upload_stream));
+    }
+    dst.n_draws = (uint32_t)draws.size();
+    dst.n_prims = (uint32_t)n_prims;
+    I->ov_version = nv;
+    return RFW_HIP_OK;
+}
+
+void release_overlay(Instance* I)
+{
+    for (auto& v : I->ov) { v.vertices.release(); v.draws.release(); v.n_draws = v.n_prims = 0; }
+    I->d_ov_prims.release(); I->d_ov_tap.release(); I->d_ov_words.release();
+    I->ov_frame_prims = I->ov_frame_words = 0;
+    if (I->ov_ready) { (void)hipEventDestroy(I->ov_ready); I->ov_ready = nullptr; }
+}
+
 int do_synchronize(Instance* I)
 {
     HIP_TRY(I, hipSetDevice(I->device));
+    if (I->ov_dirty) { // (first: a refusal leaves the scene as it was; the 2D layer is no part of the traced scene, so no image restarts)
+        const int orc = upload_overlay(I);
+        if (orc != RFW_HIP_OK) return orc;
+        I->ov_dirty = false;
+    }
     bool any_change = false;
     int rc;
     // A new (mesh, skin) pair needs its region of the mega-buffers, i.e. a BLAS rebuild: decided FIRST, so that everything below —
@@ -1163,8 +1236,31 @@ int ensure_slot_tlas(Instance* S, Instance* T)
 
 extern "C" {
 
-int rfw_hip_set_2d_mesh(void* inst, uint32_t, const void*, uint32_t, int32_t) { LOCK(inst); return RFW_HIP_OK; }
-int rfw_hip_set_2d_instances(void* inst, uint32_t, const rfw_mat4*, uint32_t) { LOCK(inst); return RFW_HIP_OK; }
+int rfw_hip_set_2d_mesh(void* inst, uint32_t id, const void* vertices, uint32_t n, int32_t tex_id)
+{
+    LOCK(inst);
+    if (n && !vertices) return fail(I, RFW_HIP_E_INVALID, "set_2d_mesh: null vertices");
+    if (n == 0 && I->meshes_2d.find(id) == I->meshes_2d.end()) return RFW_HIP_OK; // an empty mesh nobody knows: nothing to remember
+    Instance::Mesh2D& m = I->meshes_2d[id];
+    const rfw_vertex_2d* v = static_cast<const rfw_vertex_2d*>(vertices);
+    m.vertices.assign(v, v + n);
+    m.tex = tex_id < 0 ? -1 : tex_id;
+    if (m.vertices.empty() && m.matrices.empty()) I->meshes_2d.erase(id); // emptied and without instances: forgotten
+    I->ov_dirty = true;
+    return RFW_HIP_OK;
+}
+
+int rfw_hip_set_2d_instances(void* inst, uint32_t mesh, const rfw_mat4* matrices, uint32_t n)
+{
+    LOCK(inst);
+    if (n && !matrices) return fail(I, RFW_HIP_E_INVALID, "set_2d_instances: null matrices");
+    if (n == 0 && I->meshes_2d.find(mesh) == I->meshes_2d.end()) return RFW_HIP_OK;
+    Instance::Mesh2D& m = I->meshes_2d[mesh];
+    m.matrices.assign(matrices, matrices + n);
+    if (m.vertices.empty() && m.matrices.empty()) I->meshes_2d.erase(mesh);
+    I->ov_dirty = true;
+    return RFW_HIP_OK;
+}
 
 // The host copy of a mesh: the records, and their 48-B heads beside them (MeshHost).  Several threads for a large mesh (one thread moves
 // ~10 GB/s: 185 MB of C4 took 18 of the 45 ms a re-sent scene cost before anything reached the device).  A mesh of >= 128 KB is registered

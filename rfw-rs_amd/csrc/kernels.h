@@ -140,6 +140,51 @@ struct DnMotionLaunch {
 void launch_dn_ids(hipStream_t s, const CameraParams& cam, const PathDev& p, uint32_t* ids, uint32_t pixel_mask);
 void launch_dn_motion(hipStream_t s, const rfw_mat4* matrices, const InstanceXform* xf, const InstanceNormal* nm, uint32_t n, const void* prev, uint32_t n_prev,
                       void* cur, void* records);
+// The 2D layer (overlay.inc, DESIGN.md "2D layer"): the trait's 2D meshes drawn over the finalised frame, in place, behind whichever of
+// launch_assemble / launch_ao_filter / launch_atrous wrote it.  A draw is one (mesh, instance) pair; draws are sorted by (mesh id, instance
+// index) and the primitives of the frame are their triangles in that order (the draw position).  Three launches per frame:
+//   setup   one thread per primitive: transform, snap, edge functions, record (OvPrim) and debug tap (OvTap)
+//   bin     one wavefront per 64 x 64 pixels: word c of a bin = the ballot of "the box of primitive 64 c + lane touches the bin"
+//   raster  one workgroup per 16 x 16 pixels, one pixel per lane: walks its bin's words in draw order and blends in registers
+constexpr uint32_t kOvMaxPrims = 1u << 20; // triangles x instances of one frame
+constexpr uint32_t kOvBin = 64, kOvTile = 16;
+struct OvDraw {
+    float m[16];           // the instance matrix, column-major
+    uint32_t first_prim;   // draw position of its triangle 0
+    uint32_t n_tris;
+    uint32_t first_vertex; // of its mesh in the vertex array
+    uint32_t mesh, instance;
+    int32_t tex;           // texture of set_textures, < 0: none
+    uint32_t pad[2];
+};
+static_assert(sizeof(OvDraw) == 96, "OvDraw");
+struct OvTap { // rfw_hip_debug_read "ov_prims"
+    int32_t X[3], Y[3]; // the snapped vertices (8 sub-pixel bits), in the caller's vertex order
+    uint32_t mesh, instance, triangle, dropped;
+    uint32_t pad[2];
+};
+static_assert(sizeof(OvTap) == 48, "OvTap");
+struct OvPrim {
+    // edge i runs from vertex i to vertex i + 1 (after the swap that makes the doubled area S positive):
+    // E_i at the centre of pixel (px, py) = C[i] + 256 (A[i] px + B[i] py); covered iff every E_i >= need[i] (1, or 0 on a top or left edge)
+    int64_t C[3];
+    int64_t S;
+    int32_t A[3], B[3];
+    int32_t need[3];
+    int32_t tex;            // < 0: untextured
+    int32_t x0, y0, x1, y1; // pixels whose centre can be covered, clipped to the frame; x0 > x1: none (dropped, or outside)
+    float uv[3][2];
+    float color[3][4];
+};
+static_assert(sizeof(OvPrim) == 160, "OvPrim");
+struct OvFrame {
+    float view[16]; // CameraView2D::matrix, column-major
+    uint32_t width, height;
+    uint32_t n_prims, n_draws, n_textures;
+    uint32_t bins_x, bins_y, chunks; // bins of kOvBin pixels; words per bin = ceil(n_prims / 64)
+};
+void launch_overlay(hipStream_t s, const OvFrame& f, const rfw_vertex_2d* vertices, const OvDraw* draws, OvPrim* prims, OvTap* tap, uint64_t* words,
+                    const uint32_t* tex_data, const TexDesc* tex_desc, float4* frame);
 void launch_eval_shading(hipStream_t s, const SceneDev& sc, const CameraParams& cam, int op, uint32_t n, const float* in, float* out);
 void launch_query_closest(hipStream_t s, const SceneDev& sc, const float* origins, const float* directions, float t_min, float t_max, uint64_t n,
                           rfw_hip_hit* hits, uint32_t* depth = nullptr /* optional: nodes visited per ray */);

@@ -1520,4 +1520,6 @@ void launch_query_any(hipStream_t s, const SceneDev& sc, const float* origins, c
 // ---------------------------------------------------------------- option "denoise": the guided a-trous filter of the path-traced frame
 #include "denoise.inc"
 
+#include "overlay.inc"
+
 } // namespace rfwhip

@@ -8,10 +8,13 @@
 // Where the reference presents to a window, this program downloads the presented (Bgra8UnormSrgb) frame of every frame into a ring of
 // pinned host buffers without stalling the frames in flight, and writes the last one as a PPM image.
 //
-//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--out last.ppm]
+//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--hud] [--out last.ppm]
 //
 // --denoise K (off by default) finalises every frame with K a-trous passes and a history of 16 samples that follows the bouncing
 // instances (options "denoise", "denoise_temporal", "denoise_motion"): every frame here is a new image of one sample per pixel.
+// --hud (off by default) draws the frame counter and the frame time over the image the way rfw-font draws the reference's FPS counter: one
+// atlas texture (white, the glyphs in alpha, one mip level), one 2D mesh of glyph quads rewritten every frame, one 2D instance with the
+// pixel-space matrix, and the frame's Camera2D view (line 1: "frame N", line 2: "T ms" of the frame before).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +31,7 @@ int main(int argc, char** argv)
     std::string gltf, out = "example_animated.ppm";
     std::vector<std::string> actors;
     uint32_t frames = 240, width = 1280, height = 720, nx = 100, nz = 100, path_length = 2, denoise = 0;
+    bool hud = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -38,6 +42,7 @@ int main(int argc, char** argv)
         else if (a == "--spheres") std::sscanf(next(), "%ux%u", &nx, &nz);
         else if (a == "--path-length") path_length = (uint32_t)std::atoi(next());
         else if (a == "--denoise") denoise = (uint32_t)std::atoi(next());
+        else if (a == "--hud") hud = true;
         else if (a == "--out") out = next();
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -66,6 +71,19 @@ int main(int argc, char** argv)
         rfw::add_sphere_grid(scene, nx, nz, spacing);
         const uint32_t grid_mesh = scene.meshes_3d.rbegin()->first;
 
+        uint32_t hud_mesh = 0;
+        int32_t hud_atlas = -1;
+        const rfw::Camera2D camera_2d = rfw::Camera2D::from_width_height(width, height);
+        if (hud) {
+            hud_atlas = (int32_t)scene.textures.size();
+            scene.textures.push_back(rfw::hud_font_atlas());
+            scene.textures_changed = true;
+            rfw::Mesh2D text;
+            text.tex_id = hud_atlas;
+            hud_mesh = scene.add_2d_mesh(text);
+            scene.add_2d_instance(hud_mesh, rfw::hud_pixel_matrix(width, height));
+        }
+
         rfw_hip_options opt;
         std::memset(&opt, 0, sizeof(opt));
         opt.struct_size = sizeof(opt);
@@ -87,11 +105,29 @@ int main(int argc, char** argv)
         rfw::synchronize_system(scene, *renderer); // first synchronize: uploads and builds everything
         const auto t0 = std::chrono::steady_clock::now();
         uint64_t rays = 0;
+        auto t_prev = t0;
+        double ms_prev = 0.0;
         for (uint32_t f = 0; f < frames; f++) {
+            if (hud) { // the glyph mesh of this frame
+                const float white[4] = {1, 1, 1, 1};
+                const float scale = width >= 640 ? 2.0f : 1.0f;
+                char line[64];
+                rfw::Mesh2D text;
+                text.tex_id = hud_atlas;
+                std::snprintf(line, sizeof(line), "frame %u", f);
+                rfw::hud_append_text(text, line, 0.0f, 1.0f, scale, white);
+                std::snprintf(line, sizeof(line), "%.2f ms", ms_prev);
+                rfw::hud_append_text(text, line, 0.0f, 1.0f + 9.0f * scale, scale, white);
+                scene.set_2d_mesh(hud_mesh, text);
+            }
             rfw::animate_sphere_grid(scene, grid_mesh, nx, nz, spacing, (float)f / 60.0f); // bounce_spheres at 60 Hz
             scene.set_animations_time((double)f / 60.0);                                   // set_animation_timers
             rfw::synchronize_system(scene, *renderer);                                    // changed instance lists -> TLAS of this frame
-            rfw::render_system(camera, width, height, *renderer);
+            if (hud) rfw::render_system(camera, camera_2d, width, height, *renderer);
+            else rfw::render_system(camera, width, height, *renderer);
+            const auto t_now = std::chrono::steady_clock::now();
+            ms_prev = std::chrono::duration<double, std::milli>(t_now - t_prev).count();
+            t_prev = t_now;
             uint32_t* dst = ring[f % ring.size()];
             if (f >= ring.size() && rfw_hip_wait_download(renderer->raw(), dst) != RFW_HIP_OK) throw std::runtime_error(rfw_hip_last_error(renderer->raw()));
             if (rfw_hip_download_frame(renderer->raw(), 2, 0, (float*)dst, px) != RFW_HIP_OK) throw std::runtime_error(rfw_hip_last_error(renderer->raw()));

@@ -495,6 +495,18 @@ void synchronize_system(Scene& scene, Backend& renderer)
         scene.instances_changed[kv.first] = false;
         changed = true;
     }
+    for (auto& kv : scene.meshes_2d) { // :38-47 changed 2D meshes
+        if (!scene.mesh_2d_changed[kv.first]) continue;
+        renderer.set_2d_mesh(kv.first, kv.second.vertices.data(), (uint32_t)kv.second.vertices.size(), kv.second.tex_id);
+        scene.mesh_2d_changed[kv.first] = false;
+        changed = true;
+    }
+    for (auto& kv : scene.instances_2d) { // :49-61 changed 2D instance lists
+        if (!scene.instances_2d_changed[kv.first]) continue;
+        renderer.set_2d_instances(kv.first, kv.second.data(), (uint32_t)kv.second.size());
+        scene.instances_2d_changed[kv.first] = false;
+        changed = true;
+    }
     if (scene.textures_changed) { // :118-136
         std::vector<rfw_texture_data> t;
         for (const Texture& x : scene.textures) t.push_back(x.as_data());
@@ -529,6 +541,158 @@ void render_system(const Camera3D& camera, uint32_t width, uint32_t height, Back
 {
     const rfw_camera_view_3d view = camera.get_view(width, height);
     renderer.render(mat4_identity(), view, RFW_RENDER_DEFAULT);
+}
+
+void render_system(const Camera3D& camera, const Camera2D& camera_2d, uint32_t width, uint32_t height, Backend& renderer)
+{
+    const rfw_camera_view_3d view = camera.get_view(width, height);
+    renderer.render(camera_2d.get_view(), view, RFW_RENDER_DEFAULT);
+}
+
+// ------------------------------------------------------------------ the 2D layer's inputs
+Camera2D Camera2D::from_width_height(uint32_t width, uint32_t height, double scale_factor)
+{
+    const float s = (float)scale_factor;
+    const float w = (float)width * s / 2.0f, h = (float)height * s / 2.0f;
+    Camera2D c;
+    c.left = -w; c.right = w; c.bottom = -h; c.top = h; c.near_plane = 10.0f; c.far_plane = -10.0f;
+    return c;
+}
+
+rfw_mat4 Camera2D::get_view() const // glam Mat4::orthographic_rh(left, right, bottom, top, near, far)
+{
+    const float rcp_width = 1.0f / (right - left), rcp_height = 1.0f / (top - bottom), r = 1.0f / (near_plane - far_plane);
+    rfw_mat4 m;
+    std::memset(&m, 0, sizeof(m));
+    m.m[0] = rcp_width + rcp_width;
+    m.m[5] = rcp_height + rcp_height;
+    m.m[10] = r;
+    m.m[12] = -(left + right) * rcp_width;
+    m.m[13] = -(top + bottom) * rcp_height;
+    m.m[14] = r * near_plane;
+    m.m[15] = 1.0f;
+    return m;
+}
+
+static rfw_vertex_2d vertex_2d(float x, float y, float z, float u, float v, const float colour[4])
+{
+    rfw_vertex_2d o;
+    o.vertex[0] = x; o.vertex[1] = y; o.vertex[2] = z;
+    o.tex = 0;
+    o.uv[0] = u; o.uv[1] = v;
+    for (int c = 0; c < 4; c++) o.color[c] = colour[c];
+    return o;
+}
+
+Mesh2D make_quad_2d(const float bl[2], const float tr[2], float layer, int32_t tex, const float colour[4])
+{
+    Mesh2D m;
+    m.tex_id = tex < 0 ? -1 : tex;
+    m.vertices = {vertex_2d(bl[0], bl[1], layer, 0, 0, colour), vertex_2d(tr[0], bl[1], layer, 1, 0, colour), vertex_2d(tr[0], tr[1], layer, 1, 1, colour),
+                  vertex_2d(bl[0], bl[1], layer, 0, 0, colour), vertex_2d(tr[0], tr[1], layer, 1, 1, colour), vertex_2d(bl[0], tr[1], layer, 0, 1, colour)};
+    return m;
+}
+
+uint32_t Scene::add_2d_mesh(const Mesh2D& m)
+{
+    const uint32_t id = meshes_2d.empty() ? 0u : meshes_2d.rbegin()->first + 1u;
+    meshes_2d[id] = m;
+    mesh_2d_changed[id] = true;
+    return id;
+}
+void Scene::set_2d_mesh(uint32_t id, const Mesh2D& m)
+{
+    meshes_2d[id] = m;
+    mesh_2d_changed[id] = true;
+}
+uint32_t Scene::add_2d_quad(const float bl[2], const float tr[2], float layer, int32_t tex, const float colour[4]) { return add_2d_mesh(make_quad_2d(bl, tr, layer, tex, colour)); }
+size_t Scene::add_2d_instance(uint32_t mesh, const rfw_mat4& m)
+{
+    std::vector<rfw_mat4>& l = instances_2d[mesh];
+    l.push_back(m);
+    instances_2d_changed[mesh] = true;
+    return l.size() - 1;
+}
+void Scene::set_2d_matrix(uint32_t mesh, size_t slot, const rfw_mat4& m)
+{
+    std::vector<rfw_mat4>& l = instances_2d[mesh];
+    if (slot >= l.size()) throw std::out_of_range("set_2d_matrix: no such instance");
+    l[slot] = m;
+    instances_2d_changed[mesh] = true;
+}
+void Scene::remove_2d_instance(uint32_t mesh, size_t slot)
+{
+    rfw_mat4 zero;
+    std::memset(&zero, 0, sizeof(zero));
+    set_2d_matrix(mesh, slot, zero);
+}
+
+// ---- the bitmap font of the HUD: 8 x 8, drawn for this project; bit 7 of a row is its leftmost pixel
+const char kHudChars[] = "0123456789.: frames";
+static const uint8_t kHudFont[][8] = {
+    {0x3c, 0x66, 0x6e, 0x76, 0x66, 0x66, 0x3c, 0x00}, // 0
+    {0x18, 0x38, 0x18, 0x18, 0x18, 0x18, 0x7e, 0x00}, // 1
+    {0x3c, 0x66, 0x06, 0x0c, 0x30, 0x60, 0x7e, 0x00}, // 2
+    {0x3c, 0x66, 0x06, 0x1c, 0x06, 0x66, 0x3c, 0x00}, // 3
+    {0x0c, 0x1c, 0x2c, 0x4c, 0x7e, 0x0c, 0x0c, 0x00}, // 4
+    {0x7e, 0x60, 0x7c, 0x06, 0x06, 0x66, 0x3c, 0x00}, // 5
+    {0x3c, 0x60, 0x7c, 0x66, 0x66, 0x66, 0x3c, 0x00}, // 6
+    {0x7e, 0x06, 0x0c, 0x18, 0x30, 0x30, 0x30, 0x00}, // 7
+    {0x3c, 0x66, 0x66, 0x3c, 0x66, 0x66, 0x3c, 0x00}, // 8
+    {0x3c, 0x66, 0x66, 0x3e, 0x06, 0x06, 0x3c, 0x00}, // 9
+    {0x00, 0x00, 0x00, 0x00, 0x00, 0x18, 0x18, 0x00}, // .
+    {0x00, 0x18, 0x18, 0x00, 0x18, 0x18, 0x00, 0x00}, // :
+    {0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00}, // space
+    {0x1c, 0x30, 0x7c, 0x30, 0x30, 0x30, 0x30, 0x00}, // f
+    {0x00, 0x00, 0x6c, 0x76, 0x60, 0x60, 0x60, 0x00}, // r
+    {0x00, 0x00, 0x3c, 0x06, 0x3e, 0x66, 0x3e, 0x00}, // a
+    {0x00, 0x00, 0x6c, 0x7e, 0x6a, 0x62, 0x62, 0x00}, // m
+    {0x00, 0x00, 0x3c, 0x66, 0x7e, 0x60, 0x3c, 0x00}, // e
+    {0x00, 0x00, 0x3e, 0x60, 0x3c, 0x06, 0x7c, 0x00}, // s
+};
+static int hud_glyph_index(char c)
+{
+    for (int k = 0; kHudChars[k]; k++)
+        if (kHudChars[k] == c) return k;
+    return -1;
+}
+const uint8_t* hud_glyph_rows(char c)
+{
+    const int k = hud_glyph_index(c);
+    return k < 0 ? nullptr : kHudFont[k];
+}
+Texture hud_font_atlas()
+{
+    const uint32_t n = (uint32_t)(sizeof(kHudFont) / sizeof(kHudFont[0]));
+    Texture t;
+    t.width = n * kHudGlyph; t.height = kHudGlyph; t.mip_levels = 1; t.format = RFW_FORMAT_BGRA8;
+    t.bytes.assign((size_t)t.width * t.height * 4, 255);
+    for (uint32_t g = 0; g < n; g++)
+        for (uint32_t y = 0; y < kHudGlyph; y++)
+            for (uint32_t x = 0; x < kHudGlyph; x++)
+                t.bytes[((size_t)y * t.width + g * kHudGlyph + x) * 4 + 3] = ((kHudFont[g][y] >> (7 - x)) & 1) ? 255 : 0;
+    return t;
+}
+void hud_append_text(Mesh2D& mesh, const std::string& text, float x, float y, float scale, const float colour[4])
+{
+    const float n = (float)(sizeof(kHudFont) / sizeof(kHudFont[0]));
+    const float size = (float)kHudGlyph * scale;
+    for (size_t k = 0; k < text.size(); k++) {
+        const int g = hud_glyph_index(text[k]);
+        if (g < 0 || text[k] == ' ') continue; // (a space, or a character the font lacks, advances only)
+        const float x0 = x + (float)k * size, x1 = x0 + size, y0 = y, y1 = y + size;
+        const float u0 = (float)g / n, u1 = (float)(g + 1) / n; // row 0 of the atlas is the glyph's top row, and y runs down in pixel units
+        mesh.vertices.push_back(vertex_2d(x0, y0, 0, u0, 0, colour)); mesh.vertices.push_back(vertex_2d(x1, y0, 0, u1, 0, colour)); mesh.vertices.push_back(vertex_2d(x1, y1, 0, u1, 1, colour));
+        mesh.vertices.push_back(vertex_2d(x0, y0, 0, u0, 0, colour)); mesh.vertices.push_back(vertex_2d(x1, y1, 0, u1, 1, colour)); mesh.vertices.push_back(vertex_2d(x0, y1, 0, u0, 1, colour));
+    }
+}
+rfw_mat4 hud_pixel_matrix(uint32_t width, uint32_t height)
+{
+    rfw_mat4 m = mat4_identity();
+    m.m[5] = -1.0f;
+    m.m[12] = -(float)width / 2.0f;
+    m.m[13] = (float)height / 2.0f;
+    return m;
 }
 
 // ------------------------------------------------------------------ geometry helpers
@@ -1268,13 +1432,21 @@ struct rfwhost_backend_table {
     int (*set_textures)(void*, const rfw_texture_data*, uint32_t, const uint32_t*);
     int (*set_skybox)(void*, const rfw_texture_data*);
     int (*set_skins)(void*, const rfw_skin_data*, uint32_t, const uint32_t*);
+    int (*set_2d_mesh)(void*, uint32_t, const void*, uint32_t, int32_t);      // null: a backend without a 2D layer
+    int (*set_2d_instances)(void*, uint32_t, const rfw_mat4*, uint32_t);
 };
 struct TableBackend : rfw::Backend {
     rfwhost_backend_table t;
     int rc = 0;
     void acc(int r) { if (r != 0 && rc == 0) rc = r; }
-    void set_2d_mesh(size_t, const void*, uint32_t, int32_t) override {}
-    void set_2d_instances(size_t, const rfw_mat4*, uint32_t) override {}
+    void set_2d_mesh(size_t id, const void* v, uint32_t n, int32_t tex) override
+    {
+        if (t.set_2d_mesh) acc(t.set_2d_mesh(t.instance, (uint32_t)id, v, n, tex));
+    }
+    void set_2d_instances(size_t mesh, const rfw_mat4* m, uint32_t n) override
+    {
+        if (t.set_2d_instances) acc(t.set_2d_instances(t.instance, (uint32_t)mesh, m, n));
+    }
     void set_3d_mesh(size_t id, const rfw_mesh_data_3d& d) override { acc(t.set_3d_mesh(t.instance, (uint32_t)id, &d)); }
     void unload_3d_meshes(const std::vector<size_t>& ids) override
     {
@@ -1583,9 +1755,74 @@ HOST_API int rfwhost_camera_move(void* p, int op, const float* a, const float* b
 }
 HOST_API int rfwhost_set_aspect(void* p, float aspect) { ((HostScene*)p)->cam.aspect_ratio = aspect; return 0; }
 HOST_API int rfwhost_camera_view(void* p, uint32_t w, uint32_t h, rfw_camera_view_3d* out) { *out = ((HostScene*)p)->cam.get_view(w, h); return 0; }
+// ---- the 2D layer: Scene::add_2d_mesh / set_2d_mesh / add_2d_quad / add_2d_instance / set_2d_matrix / remove_2d_instance, Camera2D
+HOST_API int rfwhost_add_2d_mesh(void* p, const rfw_vertex_2d* v, uint32_t n, int32_t tex)
+{
+    rfw::Mesh2D m;
+    if (v) m.vertices.assign(v, v + n);
+    m.tex_id = tex < 0 ? -1 : tex;
+    return (int)((HostScene*)p)->scene.add_2d_mesh(m);
+}
+HOST_API int rfwhost_set_2d_mesh(void* p, uint32_t id, const rfw_vertex_2d* v, uint32_t n, int32_t tex)
+{
+    rfw::Mesh2D m;
+    if (v) m.vertices.assign(v, v + n);
+    m.tex_id = tex < 0 ? -1 : tex;
+    ((HostScene*)p)->scene.set_2d_mesh(id, m);
+    return 0;
+}
+HOST_API int rfwhost_add_2d_quad(void* p, const float* bottom_left, const float* top_right, float layer, int32_t tex, const float* colour)
+{
+    if (!bottom_left || !top_right || !colour) return -1;
+    return (int)((HostScene*)p)->scene.add_2d_quad(bottom_left, top_right, layer, tex, colour);
+}
+HOST_API int rfwhost_add_2d_instance(void* p, uint32_t mesh, const float* m16)
+{
+    rfw_mat4 m;
+    std::memcpy(m.m, m16, sizeof(m.m));
+    return (int)((HostScene*)p)->scene.add_2d_instance(mesh, m);
+}
+HOST_API int rfwhost_set_2d_matrix(void* p, uint32_t mesh, uint32_t slot, const float* m16)
+{
+    HostScene& h = *(HostScene*)p;
+    auto it = h.scene.instances_2d.find(mesh);
+    if (it == h.scene.instances_2d.end() || slot >= it->second.size()) return -1;
+    rfw_mat4 m;
+    if (m16) std::memcpy(m.m, m16, sizeof(m.m));
+    else std::memset(&m, 0, sizeof(m)); // remove_2d_instance
+    h.scene.set_2d_matrix(mesh, slot, m);
+    return 0;
+}
+// the vertices of 2D mesh `id` (40 bytes each) into out[0 .. cap): returns their number, -1: no such mesh; *tex = its texture or -1
+HOST_API int rfwhost_2d_mesh(void* p, uint32_t id, rfw_vertex_2d* out, uint32_t cap, int32_t* tex)
+{
+    HostScene& h = *(HostScene*)p;
+    auto it = h.scene.meshes_2d.find(id);
+    if (it == h.scene.meshes_2d.end()) return -1;
+    const uint32_t n = (uint32_t)it->second.vertices.size();
+    if (out) std::memcpy(out, it->second.vertices.data(), sizeof(rfw_vertex_2d) * std::min(n, cap));
+    if (tex) *tex = it->second.tex_id;
+    return (int)n;
+}
+HOST_API int rfwhost_camera_2d_view(uint32_t w, uint32_t h, double scale, float* out16)
+{
+    const rfw_mat4 m = rfw::Camera2D::from_width_height(w, h, scale).get_view();
+    std::memcpy(out16, m.m, sizeof(m.m));
+    return 0;
+}
+// the HUD font: the eight rows of `c` (bit 7 = leftmost pixel) into rows8; -1: not in the font
+HOST_API int rfwhost_hud_glyph(char c, uint8_t* rows8)
+{
+    const uint8_t* r = rfw::hud_glyph_rows(c);
+    if (!r) return -1;
+    std::memcpy(rows8, r, 8);
+    return 0;
+}
 HOST_API int rfwhost_mark_all_changed(void* p)
 {
     HostScene& h = *(HostScene*)p;
+    for (auto& kv : h.scene.meshes_2d) h.scene.mesh_2d_changed[kv.first] = true;
+    for (auto& kv : h.scene.instances_2d) h.scene.instances_2d_changed[kv.first] = true;
     for (auto& kv : h.scene.meshes_3d) h.scene.mesh_changed[kv.first] = true;
     for (auto& kv : h.scene.instances_3d) h.scene.instances_changed[kv.first] = true;
     h.scene.materials_changed = true;

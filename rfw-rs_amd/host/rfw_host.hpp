@@ -175,6 +175,33 @@ struct Camera3D {
     void look_at(const float origin[3], const float target[3]);
 };
 
+// crates/rfw-scene/src/camera/mod.rs:306-354 Camera2D: the view of the 2D layer, glam's orthographic_rh over its dimensions
+struct Camera2D {
+    float left = -1, right = 1, bottom = -1, top = 1, near_plane = 10, far_plane = -10;
+    static Camera2D from_width_height(uint32_t width, uint32_t height, double scale_factor = 1.0);
+    rfw_mat4 get_view() const; // CameraView2D::matrix
+};
+
+// crates/rfw-scene/src/objects_2d: a triangle list of Vertex2D and the texture it is drawn with (-1: none)
+struct Mesh2D {
+    std::vector<rfw_vertex_2d> vertices;
+    int32_t tex_id = -1;
+};
+// objects_2d/quad.rs Quad2D::into_mesh_2d: six vertices — bottom left, bottom right, top right; bottom left, top right, top left — with
+// uv (0, 0) at the bottom left and (1, 1) at the top right
+Mesh2D make_quad_2d(const float bottom_left[2], const float top_right[2], float layer, int32_t tex, const float colour[4]);
+
+// The text plumbing of rfw-font in small: an 8 x 8 bitmap font (digits, '.', ':', space and the letters of "frame" and "ms") as ONE atlas
+// texture — a row of glyph cells, white with the glyph in alpha, one mip level — and a string as one Mesh2D of glyph quads in pixel units
+// (y down), `scale` pixels per font pixel.  Drawn with ONE instance whose matrix is hud_pixel_matrix: scale(1, -1, 1) * translate(-w/2, -h/2, 0).
+constexpr uint32_t kHudGlyph = 8;
+struct Texture;
+extern const char kHudChars[];                 // the characters of the font, in atlas order
+const uint8_t* hud_glyph_rows(char c);         // eight rows, bit 7 = the leftmost pixel; nullptr: not in the font
+Texture hud_font_atlas();
+void hud_append_text(Mesh2D& mesh, const std::string& text, float x, float y, float scale, const float colour[4]);
+rfw_mat4 hud_pixel_matrix(uint32_t width, uint32_t height);
+
 // crates/rfw-backend/src/structs.rs:69-121 TextureData: 4 bytes per texel, mip levels concatenated (level i is (w >> i) x (h >> i))
 struct Texture {
     uint32_t width = 0, height = 0, mip_levels = 1;
@@ -263,6 +290,17 @@ struct Scene {
     std::vector<uint32_t> texture_changed_bits; // like material_changed_bits: which textures changed since the last synchronize_system; empty = all
     std::vector<uint32_t> removed_meshes; // unloaded since the last synchronize_system (rfw/src/system/mod.rs: unload_3d_meshes)
 
+    // the 2D layer (crates/rfw-scene/src/lib.rs add_2d / objects_2d, instances_2d.rs): meshes, their instance matrices, change flags
+    std::map<uint32_t, Mesh2D> meshes_2d;
+    std::map<uint32_t, std::vector<rfw_mat4>> instances_2d;
+    std::map<uint32_t, bool> mesh_2d_changed, instances_2d_changed;
+    uint32_t add_2d_mesh(const Mesh2D& m);
+    void set_2d_mesh(uint32_t id, const Mesh2D& m); // same id, new vertices (text that changes every frame)
+    uint32_t add_2d_quad(const float bottom_left[2], const float top_right[2], float layer, int32_t tex, const float colour[4]);
+    size_t add_2d_instance(uint32_t mesh, const rfw_mat4& m);
+    void set_2d_matrix(uint32_t mesh, size_t slot, const rfw_mat4& m);
+    void remove_2d_instance(uint32_t mesh, size_t slot); // a zero matrix, as instances_2d.rs make_invalid: the slot draws nothing
+
     uint32_t add_material(const Material& m);
     uint32_t add_mesh(const Mesh3D& m);
     void replace_mesh(uint32_t id, const Mesh3D& m);   // same id, new geometry (set_3d_mesh again at the next synchronize_system)
@@ -286,6 +324,7 @@ rfw_mat4 mat4_from_trs(const float t[3], const float axis[3], float angle, float
 void synchronize_system(Scene& scene, Backend& renderer);
 // rfw/src/lib.rs:411-430
 void render_system(const Camera3D& camera, uint32_t width, uint32_t height, Backend& renderer);
+void render_system(const Camera3D& camera, const Camera2D& camera_2d, uint32_t width, uint32_t height, Backend& renderer); // with the 2D layer's view
 
 // ---- synthetic scenes standing in for the assets the reference does not ship ----
 MeshDescriptor make_quad(const float normal[3], const float position[3], float width, float height, uint32_t mat_id); // objects_3d/quad.rs:19-75 Quad3D

@@ -40,6 +40,11 @@ class Vertex3D(C.Structure):
     _fields_ = [("vertex", Vec4), ("normal", Vec3), ("mat_id", u32), ("uv", Vec2), ("pad0", f32), ("pad1", f32), ("tangent", Vec4)]
 
 
+class Vertex2D(C.Structure):
+    """rfw_backend::Vertex2D, the vertices of set_2d_mesh (`tex` is ignored: the mesh's tex_id decides)."""
+    _fields_ = [("vertex", f32 * 3), ("tex", u32), ("uv", f32 * 2), ("color", f32 * 4)]
+
+
 class JointData(C.Structure):
     _fields_ = [("joint", u32 * 4), ("weight", Vec4)]
 
@@ -138,7 +143,7 @@ class Hit(C.Structure):
 
 # the reference's only boundary test, restated: backends/metal/src/lib.rs:270-348 (size_of Rust == size_of C)
 EXPECTED_SIZES = {
-    Vec2: 8, Vec3: 12, Vec4: 16, Mat4: 64, Aabb: 32, RTTriangle: 176, Vertex3D: 64, JointData: 32, VertexMesh: 48,
+    Vec2: 8, Vec3: 12, Vec4: 16, Mat4: 64, Aabb: 32, RTTriangle: 176, Vertex3D: 64, Vertex2D: 40, JointData: 32, VertexMesh: 48,
     DeviceMaterial: 96, CameraView3D: 128, AreaLight: 96, PointLight: 32, SpotLight: 48, DirectionalLight: 32,
 }
 for _t, _n in EXPECTED_SIZES.items():

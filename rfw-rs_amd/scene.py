@@ -14,7 +14,8 @@ class BackendTable(C.Structure):
     """Table of C entry points with the rfw_hip_* signatures (see rfw_host.cpp rfwhost_backend_table)."""
     _fields_ = [("instance", C.c_void_p)] + [(n, C.c_void_p) for n in (
         "set_3d_mesh", "unload_3d_meshes", "set_3d_instances", "set_materials", "synchronize",
-        "set_point_lights", "set_spot_lights", "set_area_lights", "set_directional_lights", "set_textures", "set_skybox", "set_skins")]
+        "set_point_lights", "set_spot_lights", "set_area_lights", "set_directional_lights", "set_textures", "set_skybox", "set_skins",
+        "set_2d_mesh", "set_2d_instances")]  # (the last two may stay null: a backend without a 2D layer)
 
 
 _lib = None
@@ -60,6 +61,14 @@ def host_lib():
         l.rfwhost_skin_matrices.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint32]
         l.rfwhost_instance_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         l.rfwhost_set_instance_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        l.rfwhost_add_2d_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32]
+        l.rfwhost_set_2d_mesh.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int32]
+        l.rfwhost_add_2d_quad.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int32, C.POINTER(C.c_float)]
+        l.rfwhost_add_2d_instance.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+        l.rfwhost_set_2d_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        l.rfwhost_2d_mesh.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32)]
+        l.rfwhost_camera_2d_view.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_float)]
+        l.rfwhost_hud_glyph.argtypes = [C.c_char, C.POINTER(C.c_uint8)]
         l.rfwhost_decode_image.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p)]
         _lib = l
     return _lib
@@ -213,6 +222,55 @@ class Scene:
         m = np.ascontiguousarray(np.asarray(matrix, np.float32).reshape(4, 4).T)  # column-major storage
         if self._l.rfwhost_set_instance_matrix(self._h, mesh, slot, m.ctypes.data_as(C.POINTER(C.c_float))) != 0:
             raise KeyError((mesh, slot))
+
+    # ---- the 2D layer (matrices: 16 column-major floats, as glam's to_cols_array gives them)
+    def add_2d_mesh(self, vertices, tex_id=None):
+        """Scene::add_2d with a Mesh2D: vertices as HipBackend.set_2d_mesh takes them; returns the mesh id."""
+        from .backend import vertices_2d
+        v = vertices_2d(vertices)
+        return int(self._l.rfwhost_add_2d_mesh(self._h, v.ctypes.data if len(v) else None, len(v), -1 if tex_id is None else int(tex_id)))
+
+    def set_2d_mesh(self, mesh, vertices, tex_id=None):
+        from .backend import vertices_2d
+        v = vertices_2d(vertices)
+        self._l.rfwhost_set_2d_mesh(self._h, mesh, v.ctypes.data if len(v) else None, len(v), -1 if tex_id is None else int(tex_id))
+
+    def add_2d_quad(self, bottom_left, top_right, layer=0.0, tex=None, colour=(1.0, 1.0, 1.0, 1.0)):
+        """Quad2D { bottom_left, top_right, layer, texture, color }.into_mesh_2d() added to the scene; returns the mesh id."""
+        return int(self._l.rfwhost_add_2d_quad(self._h, (C.c_float * 2)(*bottom_left), (C.c_float * 2)(*top_right), layer, -1 if tex is None else int(tex),
+                                               (C.c_float * 4)(*colour)))
+
+    def mesh_2d(self, mesh):
+        """(vertices as (n,) VERTEX_2D records, tex_id or None)"""
+        import numpy as np
+        from .backend import VERTEX_2D
+        tex = C.c_int32(-1)
+        n = self._l.rfwhost_2d_mesh(self._h, mesh, None, 0, C.byref(tex))
+        if n < 0:
+            raise KeyError(mesh)
+        v = np.zeros(n, VERTEX_2D)
+        self._l.rfwhost_2d_mesh(self._h, mesh, v.ctypes.data, n, C.byref(tex))
+        return v, (None if tex.value < 0 else tex.value)
+
+    def add_2d_instance(self, mesh, matrix):
+        return int(self._l.rfwhost_add_2d_instance(self._h, mesh, (C.c_float * 16)(*[float(x) for x in matrix])))
+
+    def set_2d_matrix(self, mesh, slot, matrix):
+        if self._l.rfwhost_set_2d_matrix(self._h, mesh, slot, (C.c_float * 16)(*[float(x) for x in matrix])) != 0:
+            raise KeyError((mesh, slot))
+
+    def remove_2d_instance(self, mesh, slot):
+        """the slot keeps its place and gets a zero matrix: it draws nothing"""
+        if self._l.rfwhost_set_2d_matrix(self._h, mesh, slot, None) != 0:
+            raise KeyError((mesh, slot))
+
+    @staticmethod
+    def camera_2d_view(width, height, scale=1.0):
+        """Camera2D::from_width_height(width, height, scale).get_view().matrix as 16 column-major float32"""
+        import numpy as np
+        out = np.zeros(16, np.float32)
+        host_lib().rfwhost_camera_2d_view(width, height, scale, out.ctypes.data_as(C.POINTER(C.c_float)))
+        return out
 
     def set_camera(self, pos, direction, fov=40.0, aperture=0.0, aspect=1.0):
         p = (C.c_float * 3)(*pos)

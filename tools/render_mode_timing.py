@@ -11,7 +11,15 @@ rfw_hip_bandwidth_probe reads per second, the yardstick of a pass's 64 algorithm
 non-zero setting k a second time with option "denoise_temporal" = H (DESIGN.md "Denoiser: temporal"), in the same turns; every frame of a
 timed repeat then starts a new image (reset_accumulation), for both, since that is where the history acts.  --denoise-motion 0,1 times
 every temporal setting once per listed value of option "denoise_motion" (DESIGN.md "Denoiser: motion"; 0 never names the option, so that
-a library without it can be timed through RFW_HIP_LIB), in the same turns."""
+a library without it can be timed through RFW_HIP_LIB), in the same turns.
+
+--overlay a,b,c times mode 0 with the 2D layer (DESIGN.md "2D layer"), the settings taking turns: a = a view_2d and no 2D data (the only
+setting a library from before the layer can run: RFW_HIP_LIB), b = a HUD of 2000 textured glyph quads of 12 x 16 pixels (4000 triangles),
+c = the same over one translucent panel of half the frame.  With --bandwidth it prints the layer's floor next to the probe: 32 bytes per
+touched pixel, the records (160 + 48 bytes written, 160 read per primitive) and the bin words written once (primitives and words as
+rfw_hip_debug_read "ov_stats" counts them).  The three kernels' own times are not gathered here: the layer runs inside the frame's existing
+time slot (no new event pair: rfw_hip_frame_stats keeps its layout), so they are read from a kernel trace of this tool's run,
+`rocprofv3 --kernel-trace --stats -- python3 tools/render_mode_timing.py --overlay b,c --repeats 1 --frames 20` (DESIGN.md "2D layer")."""
 import argparse
 import os
 import statistics
@@ -28,7 +36,8 @@ def main():
     ap.add_argument("--denoise-form", type=int, default=0)
     ap.add_argument("--denoise-temporal", type=int, default=0)
     ap.add_argument("--denoise-motion", default="")
-    ap.add_argument("--max-path-length", type=int, default=None)  # 1 for the modes (DESIGN.md "Render modes"), 3 with --denoise
+    ap.add_argument("--overlay", default="")
+    ap.add_argument("--max-path-length", type=int, default=None)  # 1 for the modes (DESIGN.md "Render modes"), 3 with --denoise or --overlay
     ap.add_argument("--bandwidth", action="store_true")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -39,7 +48,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     if a.max_path_length is None:
-        a.max_path_length = 3 if a.denoise else 1
+        a.max_path_length = 3 if a.denoise or a.overlay else 1
     import torch  # (the order bench.py has: torch's HIP runtime first)
     torch.cuda.init()
     from rfw_rs_amd import HipBackend, RenderMode, Scene
@@ -82,6 +91,64 @@ def main():
             print(f"bandwidth probe: {be.bandwidth_probe():.0f} GB/s (read + written); a pass moves 64 B x {px} pixels = {64e-6 * px:.1f} MB"
                   + (f", k_dn_temporal at least 128 B x {px} = {128e-6 * px:.1f} MB" if a.denoise_temporal else "")
                   + (f", k_dn_temporal_motion up to 24 B x {px} = {24e-6 * px:.1f} MB more, k_dn_ids 36 B per slab slot" if any(motions) else ""), flush=True)
+        be.close()
+        return
+    if a.overlay:
+        import numpy as np
+        from rfw_rs_amd import pod
+        settings = a.overlay.split(",")
+        w, h = a.width, a.height
+        view_2d = Scene.camera_2d_view(w, h)
+        pixel = np.eye(4, dtype=np.float32)  # scale(1, -1, 1) * translate(-w / 2, -h / 2, 0), column-major
+        pixel[1, 1], pixel[3, 0], pixel[3, 1] = -1.0, -w / 2.0, h / 2.0
+        pixel = pixel.reshape(16)
+
+        def quad(x0, y0, x1, y1, c, uv=(0.0, 0.0, 1.0, 1.0)):
+            p = [(x0, y0, uv[0], uv[1]), (x1, y0, uv[2], uv[1]), (x1, y1, uv[2], uv[3]), (x0, y0, uv[0], uv[1]), (x1, y1, uv[2], uv[3]), (x0, y1, uv[0], uv[3])]
+            return [[x, y, 0.0, 0.0, u, v, *c] for x, y, u, v in p]
+
+        if any(s != "a" for s in settings):
+            atlas = np.full((8, 128, 4), 255, np.uint8)  # 16 glyph cells, white, random glyph bits in alpha
+            atlas[..., 3] = np.random.default_rng(1).integers(0, 2, size=(8, 128), dtype=np.uint8) * 255
+            be.set_textures([pod.TextureData(128, 8, 1, atlas.ctypes.data_as(pod.C.POINTER(pod.C.c_uint8)), 0)])  # (the atrium has no textures of its own)
+            glyphs = []
+            for k in range(2000):
+                x, y, g = 40.0 + 14.0 * (k % 100), 40.0 + 18.0 * (k // 100), k % 16
+                glyphs += quad(x, y, x + 12.0, y + 16.0, (1.0, 1.0, 1.0, 1.0), (g / 16.0, 0.0, (g + 1) / 16.0, 1.0))
+            be.set_2d_mesh(0, quad(0.0, 0.0, w / 2.0, float(h), (0.1, 0.1, 0.3, 0.5)))
+            be.set_2d_mesh(1, glyphs, 0)
+            be.synchronize()
+        runs = {s: [] for s in settings}
+        # pixels a setting touches: its quads lie on whole pixels and do not overlap within a mesh (the panel counts again under the glyphs)
+        area = lambda v: sum(int((v[k + 1][0] - v[k][0]) * (v[k + 2][1] - v[k][1])) for k in range(0, len(v), 6))
+        glyph_px = area(glyphs) if any(s != "a" for s in settings) else 0
+        touched = {"a": 0, "b": glyph_px, "c": glyph_px + (w // 2) * h}
+        stats = {}
+        for rep in range(-1, a.repeats):
+            for s in settings:
+                if s != "a" or len(settings) > 1:
+                    be.set_2d_instances(0, [pixel] if s == "c" else None)
+                    be.set_2d_instances(1, [pixel] if s in "bc" else None)
+                    be.synchronize()
+                    be.framebuffer()
+                t0 = time.perf_counter()
+                for _ in range(a.warmup if rep < 0 else a.frames):
+                    be.render(view, view_2d)
+                be.framebuffer()
+                if rep >= 0:
+                    runs[s].append((time.perf_counter() - t0) * 1e3 / a.frames)
+                    if s != "a":
+                        stats[s] = be.overlay_stats()
+        for s in settings:
+            r = runs[s]
+            print(f"overlay {s}: {statistics.median(r):.3f} ms/frame (min {min(r):.3f}, max {max(r):.3f}; {what})", flush=True)
+        if a.bandwidth:
+            gbs = be.bandwidth_probe()
+            for s in settings:
+                st = stats.get(s, {"drawn": 0, "dropped": 0, "bin_words": 0})  # (the device's own counts of the setting's latest frame)
+                n_prims, words = st["drawn"] + st["dropped"], st["bin_words"]
+                nbytes = 32 * touched[s] + (160 + 48 + 160) * n_prims + 8 * words
+                print(f"overlay {s} floor: {touched[s]} touched pixels, {n_prims} primitives, {words} bin words = {nbytes / 1e6:.2f} MB = {nbytes / gbs / 1e3:.2f} us at the probe's {gbs:.0f} GB/s", flush=True)
         be.close()
         return
     be.set_option("ao_samples", a.ao_samples)
