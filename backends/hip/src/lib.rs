@@ -42,6 +42,7 @@ extern "C" {
     fn rfw_hip_synchronize(instance: *mut c_void) -> c_int;
     fn rfw_hip_render(instance: *mut c_void, view_2d: *const Mat4, view_3d: *const CameraView3D, mode: u32) -> c_int;
     fn rfw_hip_resize(instance: *mut c_void, w: u32, h: u32, scale: c_double) -> c_int;
+    fn rfw_hip_get_render_size(instance: *mut c_void, w: *mut u32, h: *mut u32) -> c_int;
     fn rfw_hip_set_point_lights(instance: *mut c_void, l: *const PointLight, n: u32, changed: *const u32) -> c_int;
     fn rfw_hip_set_spot_lights(instance: *mut c_void, l: *const SpotLight, n: u32, changed: *const u32) -> c_int;
     fn rfw_hip_set_area_lights(instance: *mut c_void, l: *const AreaLight, n: u32, changed: *const u32) -> c_int;
@@ -69,6 +70,12 @@ impl HipBackend {
             let msg = unsafe { CStr::from_ptr(rfw_hip_last_error(self.instance)) }.to_string_lossy().into_owned();
             panic!("rfw-hip: {}", msg);
         }
+    }
+    /// The size the frame is traced at, (window * scale) truncated: what `Camera3D::get_view` is asked for (rfw/src/system/mod.rs:217-223).
+    pub fn render_size(&self) -> (u32, u32) {
+        let (mut w, mut h) = (0u32, 0u32);
+        self.check(unsafe { rfw_hip_get_render_size(self.instance, &mut w, &mut h) });
+        (w, h)
     }
     /// BitSlice<Lsb0, usize> -> packed little-endian u32 words covering `n` elements (the library reads exactly n bits).  The trait does not
     /// promise `changed.len() == n` (rfw-scene builds the two from different ranges): bits past the slice read as CHANGED, so that a short

@@ -146,7 +146,33 @@ typedef struct {
     float u, v;
 } rfw_hip_hit;
 
-/* ---- FromWindowHandle::init / Drop  (crates/rfw-backend/src/lib.rs:26-33; metal: library.h:119-120) ---- */
+/* ---- FromWindowHandle::init / Drop  (crates/rfw-backend/src/lib.rs:26-33; metal: library.h:119-120) ----
+ * The render scale (rfw's Settings::scale_mode; DESIGN.md "Render scale").  width x height = (W, H) is the WINDOW size; the frame is traced at the
+ * RENDER size (RW, RH) = (max(1, (uint32_t)(W * scale)), max(1, (uint32_t)(H * scale))), the products taken in double and truncated, as every
+ * backend of the reference does.  A scale is valid when it is finite, 0 < scale <= 4 and RW, RH <= 16384: otherwise rfw_hip_create returns
+ * NULL (message: rfw_hip_last_error(NULL)) and rfw_hip_resize returns RFW_HIP_E_INVALID and leaves the instance, its frames and its history
+ * as they were.  Everything that traces, accumulates or filters runs at the render size and does not know the window: tiles, slabs, queues,
+ * the views' pixels (hand over the camera's view for RW x RH, as rfw does), render modes 1-6, the denoiser with its histories and motion
+ * records, every rfw_hip_debug_read tap, batches, samples, frame slots and sub-streams.
+ *   render size    rfw_hip_read_accumulator*, rfw_hip_download_frame(what = 1): the raw sums, n_floats = RW * RH * 4
+ *   window size    the finished frame: rfw_hip_read_framebuffer*, rfw_hip_download_frame(what = 0: n_floats = W * H * 4 | 2: W * H), the 2D
+ *                  layer (its pixel formula means the window: text stays pixel-sharp whatever the scale)
+ * Any other n_floats is RFW_HIP_E_INVALID.  Where RW == W and RH == H (scale 1, or any scale that truncates to the window) nothing is
+ * allocated or launched for the scale and every frame is what it is without one.  Otherwise one stage behind the finaliser resamples every
+ * finished frame a call leaves behind to the window size, before the 2D layer is drawn.  Option "scale_filter" = 0 nearest (the reference's
+ * quad pass) | 1 (default) bilinear when enlarging, the exact area average when shrinking; any other value is RFW_HIP_E_INVALID; a change
+ * applies from the next frame and does not restart accumulation.  The filter is integers and single IEEE operations (no contraction, the
+ * correctly rounded division).  Per axis, with R the render extent, N the window extent and x the window index, an ordered tap list:
+ *   nearest             [( ((2x + 1) R) / (2N), 1 )]                                                       (integer division)
+ *   bilinear (R <= N)   num = (2x + 1) R - N.  num < 0: [(0, 1)].  Else i0 = num / (2N), f = (float)(num % (2N)) / (float)(2N);
+ *                       f == 0 or i0 == R - 1: [(i0, 1)]; else [(i0, 1.0f - f), (i0 + 1, f)]
+ *   area (R > N)        j = (x R) / N ... ((x + 1) R - 1) / N, weight (float)o_j / (float)R, o_j = min((x + 1) R, (j + 1) N) - max(x R, j N)
+ * The value of a list per channel (x, y, z, w alike) is s = v_0 w_0, then s = s + v_k w_k in list order; a single tap of weight 1 copies.  A
+ * window pixel is the vertical list applied to the horizontal results of its source rows, rows ascending.  A tap of weight zero never
+ * exists: a NaN or Inf pixel spoils only the window pixels whose footprint contains it.
+ * Out of scope: scaled frames that are exchanged.  With (RW, RH) != (W, H), rfw_hip_create with options.world > 1 fails; rfw_hip_set_slab_output,
+ * rfw_hip_assemble_frame / _batch, rfw_hip_comm_init, rfw_hip_comm_init_loopback and rfw_hip_p2p_export / _connect fail with RFW_HIP_E_STATE;
+ * and rfw_hip_resize to such a scale on an instance that has any of those fails with RFW_HIP_E_STATE and leaves the instance untouched. */
 RFW_HIP_API void* rfw_hip_create(uint32_t width, uint32_t height, double scale, const rfw_hip_options* options);
 RFW_HIP_API void rfw_hip_destroy(void* instance);
 /* instance may be NULL: returns the message of the last failed rfw_hip_create on this thread. */
@@ -259,8 +285,11 @@ enum {
  * option "denoise" are skipped there; rfw_hip_render_batch and rfw_hip_render_samples take no view_2d and draw none.  NULL: no 2D layer
  * this frame.  With no 2D instance whose mesh has triangles, or with NULL, no extra launch is issued and nothing is allocated. */
 RFW_HIP_API int rfw_hip_render(void* instance, const rfw_mat4* view_2d, const rfw_camera_view_3d* view_3d, uint32_t mode);
-/* :63 resize */
+/* :63 resize — the window size and the render scale (see rfw_hip_create); a call that changes only the scale resizes the render size.  Every
+ * resize restarts accumulation, drops the temporal history and leaves the finished frame zeros until the next render. */
 RFW_HIP_API int rfw_hip_resize(void* instance, uint32_t width, uint32_t height, double scale);
+/* The render size (RW, RH) of the instance's window and scale. */
+RFW_HIP_API int rfw_hip_get_render_size(void* instance, uint32_t* width, uint32_t* height);
 /* :66-75 lights */
 RFW_HIP_API int rfw_hip_set_point_lights(void* instance, const rfw_point_light* lights, uint32_t num, const uint32_t* changed);
 RFW_HIP_API int rfw_hip_set_spot_lights(void* instance, const rfw_spot_light* lights, uint32_t num, const uint32_t* changed);
@@ -280,7 +309,8 @@ RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
  *                  "denoise" 0 (off, default) | 1 ... 5 a-trous passes over the path-traced frame, "denoise_colour" (> 0),
  *                  "denoise_temporal" 0 (off, default) | 1 ... 64 samples of history across images, "denoise_motion" 0 (off, default) | 1
  *                  the history follows moving instances, "sample_offset" 0 (default) ... 2^24, the first sample index of every
- *                  image — any other value of these is RFW_HIP_E_INVALID; see rfw_hip_render
+ *                  image — any other value of these is RFW_HIP_E_INVALID; see rfw_hip_render; "scale_filter" 0 nearest | 1 (default)
+                  bilinear / area: how the render-size frame becomes the window-size one (see rfw_hip_create)
  *   measurement    "count_traversal" (node / triangle / instance counters of the next frames), "timing" (HIP events per kernel),
  *                  "denoise_form" 0 | 1 | 2 (the a-trous kernel form: the faster one per step | direct | tiled; the image is the same)
  *   ray order      "shadow_order" 0 | 1 | 2 (which end any-hit traversals start from; the image is the same under every order),
@@ -295,9 +325,9 @@ RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
  *                  never | always | where the instance has frame slots (default) — csrc/lbvh.hip, k_tlas_fused)
  *   multi-GPU      "gather_format" 0 | 1 | 2, "present_rank" r (see rfw_hip_shard_info), "p2p_timeout_ms" (see rfw_hip_p2p_*) */
 RFW_HIP_API int rfw_hip_set_option(void* instance, const char* key, double value);
-/* tonemapped frame, RGBA32F, sqrt(acc/samples) (backends/gpu-rt/shaders/blit.comp:15-23); n_floats = w*h*4 */
+/* tonemapped frame, RGBA32F, sqrt(acc/samples) (backends/gpu-rt/shaders/blit.comp:15-23); n_floats = w*h*4 of the WINDOW size */
 RFW_HIP_API int rfw_hip_read_framebuffer(void* instance, float* rgba, uint64_t n_floats);
-/* raw accumulator (acPixels), RGBA32F sums */
+/* raw accumulator (acPixels), RGBA32F sums; n_floats = w*h*4 of the RENDER size (rfw_hip_get_render_size) */
 RFW_HIP_API int rfw_hip_read_accumulator(void* instance, float* rgba, uint64_t n_floats);
 RFW_HIP_API int rfw_hip_get_frame_stats(void* instance, rfw_hip_frame_stats* out);
 /* Sums the per-kernel HIP-event timings of every frame rendered since the previous drain (at most 64 frames are kept)

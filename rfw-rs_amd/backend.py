@@ -26,7 +26,7 @@ EXPORTS = [
     "rfw_hip_shard_info", "rfw_hip_set_slab_output", "rfw_hip_assemble_frame", "rfw_hip_intersect", "rfw_hip_occludes", "rfw_hip_debug_occludes_depth",
     "rfw_hip_debug_read", "rfw_hip_bandwidth_probe", "rfw_hip_depth_test", "rfw_hip_render_batch", "rfw_hip_assemble_batch",
     "rfw_hip_read_framebuffer_at", "rfw_hip_read_accumulator_at", "rfw_hip_host_alloc", "rfw_hip_host_free", "rfw_hip_download_frame",
-    "rfw_hip_wait_downloads", "rfw_hip_wait_download", "rfw_hip_srgb_steps", "rfw_hip_render_samples", "rfw_hip_set_blue_noise", "rfw_hip_debug_eval_shading", "rfw_hip_comm_unique_id", "rfw_hip_comm_init", "rfw_hip_comm_init_loopback", "rfw_hip_comm_destroy", "rfw_hip_p2p_export", "rfw_hip_p2p_connect", "rfw_hip_p2p_disconnect", "rfw_hip_intersect4", "rfw_hip_occludes4", "rfw_hip_debug_lbvh_stress", "rfw_hip_issue_probe",
+    "rfw_hip_wait_downloads", "rfw_hip_wait_download", "rfw_hip_srgb_steps", "rfw_hip_render_samples", "rfw_hip_set_blue_noise", "rfw_hip_debug_eval_shading", "rfw_hip_comm_unique_id", "rfw_hip_comm_init", "rfw_hip_comm_init_loopback", "rfw_hip_comm_destroy", "rfw_hip_p2p_export", "rfw_hip_p2p_connect", "rfw_hip_p2p_disconnect", "rfw_hip_intersect4", "rfw_hip_occludes4", "rfw_hip_debug_lbvh_stress", "rfw_hip_issue_probe", "rfw_hip_get_render_size",
 ]
 
 _lib = None
@@ -75,6 +75,7 @@ def hip_lib():
         l.rfw_hip_synchronize.argtypes = [vp]
         l.rfw_hip_render.argtypes = [vp, C.POINTER(pod.Mat4), C.POINTER(pod.CameraView3D), u32]
         l.rfw_hip_resize.argtypes = [vp, u32, u32, C.c_double]
+        l.rfw_hip_get_render_size.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
         for n in ("point", "spot", "area", "directional"):
             getattr(l, f"rfw_hip_set_{n}_lights").argtypes = [vp, vp, u32, vp]
         l.rfw_hip_set_skybox.argtypes = [vp, C.POINTER(pod.TextureData)]
@@ -170,7 +171,8 @@ class HipBackend:
 
     @classmethod
     def init(cls, width, height, scale=1.0, **options):
-        """FromWindowHandle::init(window, width, height, scale) — headless, the window handle is dropped."""
+        """FromWindowHandle::init(window, width, height, scale) — headless, the window handle is dropped; the frame is traced at
+        (width * scale, height * scale), truncated, and presented at width x height (include/rfw_hip.h, rfw_hip_create)."""
         return cls(width, height, scale, **options)
 
     def __init__(self, width, height, scale=1.0, device=-1, max_path_length=0, clamp_value=0.0, rank=0, world=1,
@@ -182,7 +184,8 @@ class HipBackend:
             raise BackendError("rfw_hip_create failed: " + self._l.rfw_hip_last_error(None).decode())
         self._h = C.c_void_p(h)
         self._pinned = {}
-        self.width, self.height = width, height
+        self.width, self.height = width, height  # the window: the finished frame, the 2D layer, the presented frame
+        self.render_width, self.render_height = self.render_size()  # what is traced: the accumulator, the denoiser's taps
         self.rank, self.world = rank, max(world, 1)
 
     def close(self):
@@ -271,6 +274,13 @@ class HipBackend:
     def resize(self, window_size, scale_factor=1.0):
         self._check(self._l.rfw_hip_resize(self._h, window_size[0], window_size[1], scale_factor))
         self.width, self.height = window_size
+        self.render_width, self.render_height = self.render_size()
+
+    def render_size(self):
+        """(width, height) the frame is traced at: (max(1, int(window width * scale)), max(1, int(window height * scale)))."""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._l.rfw_hip_get_render_size(self._h, C.byref(w), C.byref(h)))
+        return int(w.value), int(h.value)
 
     def _set_lights(self, kind, ctype, lights):
         arr = (ctype * len(lights))(*lights)
@@ -367,7 +377,7 @@ class HipBackend:
         self._check(self._l.rfw_hip_assemble_batch(self._h, C.c_void_p(gathered_ptr), count))
 
     def accumulator_at(self, frame):
-        a = np.empty((self.height, self.width, 4), dtype=np.float32)
+        a = np.empty((self.render_height, self.render_width, 4), dtype=np.float32)
         self._check(self._l.rfw_hip_read_accumulator_at(self._h, frame, a.ctypes.data, a.size))
         return a
 
@@ -376,16 +386,18 @@ class HipBackend:
         self._check(self._l.rfw_hip_read_framebuffer_at(self._h, frame, a.ctypes.data, a.size))
         return a
 
-    def host_frame(self, presented=False):
-        """A pinned (h, w, 4) array for download_frame: float32, or uint8 B,G,R,A for the presented frame; freed with free_host_frame."""
-        n = self.height * self.width * (1 if presented else 4)
+    def host_frame(self, presented=False, accumulator=False):
+        """A pinned (h, w, 4) array for download_frame: float32, or uint8 B,G,R,A for the presented frame; freed with free_host_frame.
+        accumulator: of the render size (for download_frame(accumulator=True)), else of the window size."""
+        w, h = (self.render_width, self.render_height) if accumulator and not presented else (self.width, self.height)
+        n = h * w * (1 if presented else 4)
         p = self._l.rfw_hip_host_alloc(n * 4)
         if not p:
             raise BackendError("rfw_hip_host_alloc failed")
         if presented:
-            a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self.height, self.width, 4))
+            a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(h, w, 4))
         else:
-            a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(self.height, self.width, 4))
+            a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(h, w, 4))
         self._pinned[a.ctypes.data] = p
         return a
 
@@ -417,7 +429,7 @@ class HipBackend:
         return a
 
     def accumulator(self):
-        a = np.empty((self.height, self.width, 4), dtype=np.float32)
+        a = np.empty((self.render_height, self.render_width, 4), dtype=np.float32)
         self._check(self._l.rfw_hip_read_accumulator(self._h, a.ctypes.data, a.size))
         return a
 
@@ -551,20 +563,20 @@ class HipBackend:
 
     def denoise_guide(self):
         """The denoiser's guide of the latest frame (option "denoise"): g0 = (faced gN, t), g1 = (P, 0), g2 = (albedo, f), each (H, W, 4)."""
-        g = np.frombuffer(self.debug_read("dn_guide", 48 * self.width * self.height).tobytes(), np.float32)
-        return tuple(g.reshape(3, self.height, self.width, 4))
+        g = np.frombuffer(self.debug_read("dn_guide", 48 * self.render_width * self.render_height).tobytes(), np.float32)
+        return tuple(g.reshape(3, self.render_height, self.render_width, 4))
 
     def denoise_history(self):
         """The history plane the latest denoised frame wrote (option "denoise_temporal"): (H, W, 4) = (x.rgb, h), the blended demodulated
         radiance and the samples behind it; empty before the first temporal frame."""
-        g = np.frombuffer(self.debug_read("dn_history", 16 * self.width * self.height).tobytes(), np.float32)
-        return g.reshape(-1, self.width, 4)
+        g = np.frombuffer(self.debug_read("dn_history", 16 * self.render_width * self.render_height).tobytes(), np.float32)
+        return g.reshape(-1, self.render_width, 4)
 
     def denoise_ids(self):
         """The instance ids of the latest frame's primary hits (option "denoise_motion"): (H, W) uint32, 0xffffffff where the camera ray
         missed; empty before the first frame with the option on."""
-        g = np.frombuffer(self.debug_read("dn_ids", 4 * self.width * self.height).tobytes(), np.uint32)
-        return g.reshape(-1, self.width)
+        g = np.frombuffer(self.debug_read("dn_ids", 4 * self.render_width * self.render_height).tobytes(), np.uint32)
+        return g.reshape(-1, self.render_width)
 
     def denoise_motion(self):
         """The motion records the latest temporal frame used (option "denoise_motion"), one per instance id: (A, B, state) with A (n, 3, 4) the

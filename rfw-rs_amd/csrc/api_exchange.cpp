@@ -145,6 +145,7 @@ int rfw_hip_comm_unique_id(void* out128)
 int rfw_hip_comm_init(void* inst, const void* id128, uint32_t rank, uint32_t world)
 {
     LOCK(inst);
+    REFUSE_SCALED(I, "comm_init");
     if (!id128 || world == 0 || rank >= world) return fail(I, RFW_HIP_E_INVALID, "comm_init: bad arguments");
     if (rank != I->rank || world != I->world) return fail(I, RFW_HIP_E_INVALID, "comm_init: rank / world differ from the shard this instance was created with (rfw_hip_options.rank / world)");
     if (I->substreams > 1) return fail(I, RFW_HIP_E_STATE, "comm_init: an instance with sub-streams cannot own a communicator");
@@ -293,6 +294,7 @@ extern "C" {
 int rfw_hip_comm_init_loopback(void* inst, uint64_t hub_key, uint32_t rank, uint32_t world)
 {
     LOCK(inst);
+    REFUSE_SCALED(I, "comm_init_loopback");
     if (world == 0 || world > 16 || rank >= world) return fail(I, RFW_HIP_E_INVALID, "comm_init_loopback: bad arguments (1 <= world <= 16, rank < world)");
     if (rank != I->rank || world != I->world) return fail(I, RFW_HIP_E_INVALID, "comm_init_loopback: rank / world differ from the shard this instance was created with (rfw_hip_options.rank / world)");
     if (I->substreams > 1) return fail(I, RFW_HIP_E_STATE, "comm_init_loopback: an instance with sub-streams cannot exchange through a hub");
@@ -371,6 +373,7 @@ extern "C" {
 int rfw_hip_p2p_export(void* inst, void* handle_out)
 {
     LOCK(inst);
+    REFUSE_SCALED(I, "p2p_export");
     if (!handle_out) return fail(I, RFW_HIP_E_INVALID, "p2p_export: null handle");
     if (I->scene) return fail(I, RFW_HIP_E_INVALID, "p2p_export: call it on the instance, not on a frame slot");
     if (I->substreams > 1) return fail(I, RFW_HIP_E_STATE, "p2p_export: not available with sub-streams");
@@ -424,6 +427,7 @@ int rfw_hip_p2p_export(void* inst, void* handle_out)
 int rfw_hip_p2p_connect(void* inst, const void* handles)
 {
     LOCK(inst);
+    REFUSE_SCALED(I, "p2p_connect");
     if (!handles) return fail(I, RFW_HIP_E_INVALID, "p2p_connect: null handles");
     Instance::P2P& P = I->p2p;
     if (!P.data || !P.flags) return fail(I, RFW_HIP_E_STATE, "p2p_connect: rfw_hip_p2p_export first");
@@ -492,6 +496,7 @@ int rfw_hip_shard_info(void* inst, uint64_t* slab_floats, uint32_t* local, uint3
 int rfw_hip_set_slab_output(void* inst, void* ptr)
 {
     LOCK(inst);
+    REFUSE_SCALED(I, "set_slab_output");
     if (!I->slots.empty()) return fail(I, RFW_HIP_E_STATE, "set_slab_output: not available with frames_in_flight > 1 (one instance per frame in flight instead)");
     I->external_slab = ptr;
     I->sample_count = 0;
@@ -500,6 +505,7 @@ int rfw_hip_set_slab_output(void* inst, void* ptr)
 static int assemble_impl(void* inst, const void* gathered, uint32_t k)
 {
     LOCK(inst);
+    REFUSE_SCALED(I, "assemble_frame / assemble_batch");
     if (!gathered) return fail(I, RFW_HIP_E_INVALID, "assemble_frame: null buffer");
     if (k == 0 || k > I->max_batch || (k > 1 && I->substreams > 1)) return fail(I, RFW_HIP_E_INVALID, "assemble_batch: bad frame count");
     HIP_TRY(I, hipSetDevice(I->device));

@@ -78,6 +78,11 @@ int alloc_paths(Instance* I)
     HIP_TRY(I, I->d_frame_out.ensure(px));
     I->acc_source = nullptr;
     HIP_TRY(I, hipMemsetAsync(I->d_frame_out.ptr, 0, px * sizeof(float4), I->stream));
+    if (scaled(I)) { // the window frame (zeros until the first render); the same-size path has none
+        const size_t wpx = (size_t)I->window_w * I->window_h * I->max_batch;
+        HIP_TRY(I, I->d_frame_win.ensure(wpx));
+        HIP_TRY(I, hipMemsetAsync(I->d_frame_win.ptr, 0, wpx * sizeof(float4), I->stream));
+    } else I->d_frame_win.release();
     // per-thread overflow slots: launch grids are padded (XCD tiling, shadow buckets), so leave a margin per sub-shard
     HIP_TRY(I, I->d_spill.ensure((size_t)kStackSpill * I->substreams * ((size_t)I->cap_v * I->max_batch + kSpillMargin)));
     HIP_TRY(I, I->d_counters.ensure(2 * kMaxSub));
@@ -500,20 +505,22 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         else if (mode == RFW_HIP_RENDER_FILTERED_SSAO) launch_ao_filter(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_ao_guide.ptr, I->d_frame_out.ptr, I->sample_count);
         else launch_assemble(main, cam[0], I->d_acc_slab.ptr, false, false, I->cap_v, I->d_frame_out.ptr, I->sample_count, mode != RFW_HIP_RENDER_DEFAULT);
         I->acc_source = I->d_acc_slab.ptr; I->acc_source_rgb = false; I->acc_source_batch = frames_out;
+        if (scaled(I)) // the render scale: every frame this call leaves behind -> the window size; from here on the window frame is THE frame
+            launch_resample(main, I->d_frame_out.ptr, I->width, I->height, I->d_frame_win.ptr, I->window_w, I->window_h, O->scale_filter, frames_out);
         if (ov) { // the 2D layer, in place over the frame the finaliser just wrote (behind the history's event: the history never sees it)
             const uint32_t n = ov->n_prims;
             OvFrame f;
             std::memcpy(f.view, O->view_2d->m, sizeof(f.view));
-            f.width = I->width; f.height = I->height;
+            f.width = I->window_w; f.height = I->window_h; // (the 2D layer is drawn at the window's resolution whatever the render scale)
             f.n_prims = n; f.n_draws = ov->n_draws; f.n_textures = O->n_textures;
-            f.bins_x = (I->width + kOvBin - 1u) / kOvBin; f.bins_y = (I->height + kOvBin - 1u) / kOvBin;
+            f.bins_x = (I->window_w + kOvBin - 1u) / kOvBin; f.bins_y = (I->window_h + kOvBin - 1u) / kOvBin;
             f.chunks = (n + 63u) / 64u;
             const size_t n_words = (size_t)f.bins_x * f.bins_y * f.chunks;
             HIP_TRY(I, I->d_ov_prims.ensure(n));
             HIP_TRY(I, I->d_ov_tap.ensure(n));
             HIP_TRY(I, I->d_ov_words.ensure(n_words));
             launch_overlay(main, f, ov->vertices.ptr, ov->draws.ptr, I->d_ov_prims.ptr, I->d_ov_tap.ptr, I->d_ov_words.ptr, O->d_tex_data.ptr, O->d_tex_desc.ptr,
-                           I->d_frame_out.ptr);
+                           window_frame(I));
             I->ov_frame_prims = n;
             I->ov_frame_words = (uint32_t)n_words;
         }
@@ -544,7 +551,7 @@ uint32_t rfw_hip_abi_version(void) { return RFW_HIP_ABI_VERSION; }
 uint32_t rfw_hip_selftest_index_magic(uint32_t d, uint64_t n_max) { return index_magic(d, n_max); }
 
 
-void* rfw_hip_create(uint32_t width, uint32_t height, double /*scale*/, const rfw_hip_options* o)
+void* rfw_hip_create(uint32_t width, uint32_t height, double scale, const rfw_hip_options* o)
 {
     read_env_switches(); // (the one place the library asks the environment: env_switches.h)
     int ndev = 0;
@@ -558,9 +565,20 @@ void* rfw_hip_create(uint32_t width, uint32_t height, double /*scale*/, const rf
         g_create_error = "width and height must be non-zero";
         return nullptr;
     }
+    uint32_t rw = 0, rh = 0;
+    if (!render_size_of(width, height, scale, rw, rh)) {
+        g_create_error = "scale must be finite, 0 < scale <= 4, and the render size (width x scale, height x scale) at most 16384 per axis";
+        return nullptr;
+    }
+    if ((rw != width || rh != height) && o && o->world > 1) {
+        g_create_error = "a render scale that changes the frame's size is not available with world > 1 (a scaled frame is not exchanged)";
+        return nullptr;
+    }
     Instance* I = new Instance();
-    I->width = width;
-    I->height = height;
+    I->window_w = width;
+    I->window_h = height;
+    I->width = rw;
+    I->height = rh;
     int dev = -1;
     uint32_t n_slots = 1;
     if (o) {
@@ -646,7 +664,7 @@ void* rfw_hip_create(uint32_t width, uint32_t height, double /*scale*/, const rf
         so.frames_in_flight = 1;
         so.max_batch = I->max_batch;
         for (uint32_t k = 1; k < n_slots; k++) {
-            Instance* c = static_cast<Instance*>(rfw_hip_create(width, height, 1.0, &so));
+            Instance* c = static_cast<Instance*>(rfw_hip_create(width, height, scale, &so));
             if (!c) { // g_create_error is set
                 for (Instance* d : I->slots) rfw_hip_destroy(d);
                 I->slots.clear();
@@ -721,7 +739,7 @@ void rfw_hip_destroy(void* inst)
             if (I->stage_event[k]) (void)hipEventDestroy(I->stage_event[k]);
         }
         for (int h = 0; h < 2; h++) { I->d_ray_o[h].release(); I->d_ray_d[h].release(); I->d_thr[h].release(); I->d_hit[h].release(); }
-        I->d_sh_o.release(); I->d_sh_d.release(); I->d_sh_e.release(); I->d_acc_slab.release(); I->d_frame_acc.release(); I->d_frame_out.release(); I->d_present.release();
+        I->d_sh_o.release(); I->d_sh_d.release(); I->d_sh_e.release(); I->d_acc_slab.release(); I->d_frame_acc.release(); I->d_frame_out.release(); I->d_frame_win.release(); I->d_present.release();
         I->d_dn_guide.release(); I->d_dn_plane[0].release(); I->d_dn_plane[1].release();
         I->d_dn_history[0].release(); I->d_dn_history[1].release();
         I->d_dn_ids.release(); I->d_dn_motion.release();
@@ -813,20 +831,30 @@ int rfw_hip_render_samples(void* inst, const rfw_camera_view_3d* view, uint32_t 
 }
 
 
-int rfw_hip_resize(void* inst, uint32_t w, uint32_t h, double)
+int rfw_hip_resize(void* inst, uint32_t w, uint32_t h, double scale)
 {
     LOCK(inst);
     if (w == 0 || h == 0) return fail(I, RFW_HIP_E_INVALID, "resize: zero size");
-    if (scene_of(I)->p2p.data && (w != I->width || h != I->height)) return fail(I, RFW_HIP_E_STATE, "resize: disconnect the p2p exchange first (its buffers are sized for the frame)");
+    uint32_t rw = 0, rh = 0;
+    if (!render_size_of(w, h, scale, rw, rh))
+        return fail(I, RFW_HIP_E_INVALID, "resize: scale must be finite, 0 < scale <= 4, and the render size at most 16384 per axis");
+    if (rw != w || rh != h) { // a scaled frame is not exchanged (include/rfw_hip.h): nothing has been touched yet
+        const Instance* O = scene_of(I);
+        if (I->world > 1 || O->comm || O->loop || O->p2p.data || I->external_slab)
+            return fail(I, RFW_HIP_E_STATE, "resize: a render scale that changes the frame's size is not available on an instance that exchanges its frame (world > 1, a communicator, the p2p exchange, a slab output)");
+    }
+    if (scene_of(I)->p2p.data && (rw != I->width || rh != I->height)) return fail(I, RFW_HIP_E_STATE, "resize: disconnect the p2p exchange first (its buffers are sized for the frame)");
     HIP_TRY(I, hipSetDevice(I->device));
     HIP_TRY(I, hipStreamSynchronize(I->stream));
     for (Instance* c : I->slots) {
-        const int rc = rfw_hip_resize(c, w, h, 1.0);
+        const int rc = rfw_hip_resize(c, w, h, scale);
         if (rc != RFW_HIP_OK) return fail(I, rc, c->err);
     }
     I->restart = true;
-    I->width = w;
-    I->height = h;
+    I->window_w = w;
+    I->window_h = h;
+    I->width = rw;
+    I->height = rh;
     I->dn_images = 0; // option "denoise_temporal": the history belongs to the old size
     // option "denoise_motion": so do the ids, the snapshots and the records (allocated again at the next frame that needs them)
     I->d_dn_ids.release(); I->d_dn_motion.release();
@@ -938,6 +966,10 @@ int rfw_hip_set_option(void* inst, const char* key, double value)
         if (value != 0.0 && value != 1.0 && value != 2.0) return fail(I, RFW_HIP_E_INVALID, "set_option: denoise_form is 0, 1 or 2");
         I->denoise_form = (uint32_t)value;
     }
+    else if (k == "scale_filter") { // how the render-size frame becomes the window-size one (resample.inc): 0 nearest, 1 bilinear / area; from the next frame on, the image goes on
+        if (value != 0.0 && value != 1.0) return fail(I, RFW_HIP_E_INVALID, "set_option: scale_filter is 0 (nearest) or 1 (bilinear / area)");
+        I->scale_filter = (uint32_t)value;
+    }
     else if (k == "gather_format") { // 0 f32 accumulator RGB, 1 f16 finished frame, 2 presented BGRA8 (sharded frames only)
         if (value < 0 || value > 2) return fail(I, RFW_HIP_E_INVALID, "set_option: gather_format is 0, 1 or 2");
         I->gather_format = (uint32_t)value;
@@ -998,7 +1030,9 @@ int rfw_hip_read_accumulator_at(void* inst, uint32_t frame, float* rgba, uint64_
 static int read_frame_impl(void* inst, uint32_t frame, bool accumulator, float* rgba, uint64_t n)
 {
     LOCK(inst);
-    if (!rgba || n != (uint64_t)I->width * I->height * 4) return fail(I, RFW_HIP_E_INVALID, "read_*_at: size mismatch");
+    // the accumulator lives at the render size, the finished frame at the window size
+    const uint64_t fpx = accumulator ? (uint64_t)I->width * I->height : (uint64_t)I->window_w * I->window_h;
+    if (!rgba || n != fpx * 4) return fail(I, RFW_HIP_E_INVALID, "read_*_at: size mismatch");
     if (frame >= I->max_batch) return fail(I, RFW_HIP_E_INVALID, "read_*_at: frame index beyond options.max_batch");
     if (!I->slots.empty() && I->cur_slot != 0) { // frames in flight: the latest batch lives in a slot
         Instance* c = slot_ptr(I, I->cur_slot);
@@ -1016,7 +1050,7 @@ static int read_frame_impl(void* inst, uint32_t frame, bool accumulator, float* 
         const int rc = ensure_assembled(I);
         if (rc != RFW_HIP_OK) return rc;
     }
-    const float4* src = (accumulator ? I->d_frame_acc.ptr : I->d_frame_out.ptr) + (size_t)frame * I->width * I->height;
+    const float4* src = (accumulator ? I->d_frame_acc.ptr : window_frame(I)) + (size_t)frame * fpx;
     HIP_TRY(I, hipMemcpyAsync(rgba, src, n * sizeof(float), hipMemcpyDeviceToHost, I->stream));
     HIP_TRY(I, hipStreamSynchronize(I->stream));
     CHECK_OVERFLOW(I);
@@ -1045,7 +1079,7 @@ void rfw_hip_host_free(void* p)
 int rfw_hip_download_frame(void* inst, uint32_t what, uint32_t frame, float* host_rgba, uint64_t n)
 {
     LOCK(inst);
-    const uint64_t px = (uint64_t)I->width * I->height;
+    const uint64_t px = what == 1 ? (uint64_t)I->width * I->height : (uint64_t)I->window_w * I->window_h; // accumulator: render size; finished frame: window
     if (!host_rgba || n != (what == 2 ? px : px * 4)) return fail(I, RFW_HIP_E_INVALID, "download_frame: size mismatch");
     if (what > 2 || frame >= I->max_batch) return fail(I, RFW_HIP_E_INVALID, "download_frame: bad selector");
     Instance* c = I->slots.empty() ? I : slot_ptr(I, I->cur_slot);
@@ -1067,7 +1101,7 @@ int rfw_hip_download_frame(void* inst, uint32_t what, uint32_t frame, float* hos
         c->download_dst.push_back(host_rgba);
         return RFW_HIP_OK;
     }
-    const float4* src = (what == 1 ? c->d_frame_acc.ptr : c->d_frame_out.ptr) + (size_t)frame * px;
+    const float4* src = (what == 1 ? c->d_frame_acc.ptr : window_frame(c)) + (size_t)frame * px;
     // Presented frame into a pinned destination (rfw_hip_host_alloc, or registered by the caller): the encoding kernel stores straight
     // into host memory over the link, no copy command (measured: 0.731 ms per frame against 0.762 with encode + copy, 8 frames in flight).
     // Float frames, and pageable destinations, go through the runtime's copy.
@@ -1207,6 +1241,15 @@ int rfw_hip_set_stream(void* inst, void* stream)
     HIP_TRY(I, hipSetDevice(I->device));
     HIP_TRY(I, hipStreamSynchronize(I->stream));
     I->stream = stream ? (hipStream_t)stream : I->own_stream;
+    return RFW_HIP_OK;
+}
+
+int rfw_hip_get_render_size(void* inst, uint32_t* width, uint32_t* height)
+{
+    LOCK(inst);
+    if (!width || !height) return fail(I, RFW_HIP_E_INVALID, "get_render_size: null out");
+    *width = I->width;
+    *height = I->height;
     return RFW_HIP_OK;
 }
 

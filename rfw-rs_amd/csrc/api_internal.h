@@ -254,7 +254,14 @@ struct Instance {
     std::string err;
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
+    // width x height is the RENDER size: everything that traces, accumulates or filters runs at it and knows no other.  window_w x window_h is
+    // what create / resize were handed; render = (max(1, (uint32_t)(window * scale))) per axis (DESIGN.md "Render scale").  Where the two differ
+    // the finalised frame is resampled into d_frame_win (window size, max_batch frames; not allocated otherwise) behind the finaliser, and the
+    // 2D layer, presentation, reads and downloads of the finished frame take that one: window_frame().  Option "scale_filter" (owner): 0 nearest,
+    // 1 bilinear / area.
     uint32_t width = 0, height = 0;
+    uint32_t window_w = 0, window_h = 0;
+    uint32_t scale_filter = 1;
     uint32_t max_path_length = 3;
     float clamp_value = 10.0f;
     uint32_t rank = 0, world = 1, tile_size = 64;
@@ -416,7 +423,7 @@ struct Instance {
     bool build_events_pending = false; // recorded, not read yet (rfw_hip_get_scene_stats reads them: no synchronisation for them in synchronize())
 
     // device path state
-    DevBuf<float4> d_ray_o[2], d_ray_d[2], d_thr[2], d_sh_o, d_sh_d, d_sh_e, d_acc_slab, d_frame_acc, d_frame_out;
+    DevBuf<float4> d_ray_o[2], d_ray_d[2], d_thr[2], d_sh_o, d_sh_d, d_sh_e, d_acc_slab, d_frame_acc, d_frame_out, d_frame_win;
     DevBuf<uint32_t> d_present; // BGRA8 sRGB frame, made on demand by rfw_hip_download_frame(what = 2)
     DevBuf<uint4> d_hit[2];
     // extension rays traced in spatial order (option "sort_extension_rays"): (key, queue index) pairs, sorted with hipCUB on the frame's stream
@@ -559,6 +566,22 @@ struct Instance {
     hipEvent_t frame_done = nullptr;      // per slot: recorded after its latest render; the owner waits for it before it edits the scene
 };
 
+inline bool scaled(const Instance* I) { return I->window_w != I->width || I->window_h != I->height; }
+inline float4* window_frame(Instance* I) { return scaled(I) ? I->d_frame_win.ptr : I->d_frame_out.ptr; }
+// the render size of a window under a scale; false: not a valid scale (finite, 0 < scale <= 4, at most 16384 render pixels per axis)
+inline bool render_size_of(const uint32_t w, const uint32_t h, const double scale, uint32_t& rw, uint32_t& rh)
+{
+    if (!std::isfinite(scale) || !(scale > 0.0) || !(scale <= 4.0)) return false;
+    const double x = (double)w * scale, y = (double)h * scale;
+    if (x >= 16385.0 || y >= 16385.0) return false;
+    rw = std::max(1u, (uint32_t)x);
+    rh = std::max(1u, (uint32_t)y);
+    return true;
+}
+#define REFUSE_SCALED(inst, what)                                                                                                                   \
+    do {                                                                                                                                            \
+        if (scaled(inst)) return fail(inst, RFW_HIP_E_STATE, what ": not available where the render size differs from the window size (a scaled frame is not exchanged)"); \
+    } while (0)
 inline Instance* scene_of(Instance* I) { return I->scene ? I->scene : I; }
 inline const Instance* scene_of(const Instance* I) { return I->scene ? I->scene : I; }
 void p2p_release(Instance* I);

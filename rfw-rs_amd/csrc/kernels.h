@@ -185,6 +185,9 @@ struct OvFrame {
 };
 void launch_overlay(hipStream_t s, const OvFrame& f, const rfw_vertex_2d* vertices, const OvDraw* draws, OvPrim* prims, OvTap* tap, uint64_t* words,
                     const uint32_t* tex_data, const TexDesc* tex_desc, float4* frame);
+// The render scale (resample.inc, DESIGN.md "Render scale"): `frames` finalised frames of rw x rh at `src` -> frames of w x h at `dst`; filter 0 =
+// nearest, 1 = bilinear when enlarging / exact area average when shrinking (per axis).  Issued only where the two sizes differ.
+void launch_resample(hipStream_t s, const float4* src, uint32_t rw, uint32_t rh, float4* dst, uint32_t w, uint32_t h, uint32_t filter, uint32_t frames);
 void launch_eval_shading(hipStream_t s, const SceneDev& sc, const CameraParams& cam, int op, uint32_t n, const float* in, float* out);
 void launch_query_closest(hipStream_t s, const SceneDev& sc, const float* origins, const float* directions, float t_min, float t_max, uint64_t n,
                           rfw_hip_hit* hits, uint32_t* depth = nullptr /* optional: nodes visited per ray */);

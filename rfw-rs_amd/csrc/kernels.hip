@@ -1521,5 +1521,7 @@ void launch_query_any(hipStream_t s, const SceneDev& sc, const float* origins, c
 #include "denoise.inc"
 
 #include "overlay.inc"
+// ---------------------------------------------------------------- the render scale: render-size frame -> window-size frame
+#include "resample.inc"
 
 } // namespace rfwhip

@@ -8,7 +8,7 @@
 // Where the reference presents to a window, this program downloads the presented (Bgra8UnormSrgb) frame of every frame into a ring of
 // pinned host buffers without stalling the frames in flight, and writes the last one as a PPM image.
 //
-//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--hud] [--out last.ppm]
+//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--scale S] [--hud] [--out last.ppm]
 //
 // --denoise K (off by default) finalises every frame with K a-trous passes and a history of 16 samples that follows the bouncing
 // instances (options "denoise", "denoise_temporal", "denoise_motion"): every frame here is a new image of one sample per pixel.
@@ -32,6 +32,7 @@ int main(int argc, char** argv)
     std::vector<std::string> actors;
     uint32_t frames = 240, width = 1280, height = 720, nx = 100, nz = 100, path_length = 2, denoise = 0;
     bool hud = false;
+    double scale = 1.0; // rfw's Settings::scale_mode = Custom(S): traced at size x S, presented at size
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -42,6 +43,7 @@ int main(int argc, char** argv)
         else if (a == "--spheres") std::sscanf(next(), "%ux%u", &nx, &nz);
         else if (a == "--path-length") path_length = (uint32_t)std::atoi(next());
         else if (a == "--denoise") denoise = (uint32_t)std::atoi(next());
+        else if (a == "--scale") scale = std::atof(next());
         else if (a == "--hud") hud = true;
         else if (a == "--out") out = next();
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -91,7 +93,8 @@ int main(int argc, char** argv)
         opt.max_path_length = path_length;
         opt.world = 1;
         opt.frames_in_flight = 4; // one HIP stream per frame slot
-        std::unique_ptr<rfw::HipBackend> renderer(rfw::HipBackend::init(width, height, 1.0, &opt));
+        std::unique_ptr<rfw::HipBackend> renderer(rfw::HipBackend::init(width, height, scale, &opt));
+        std::printf("window %ux%u, scale %g: traced at %ux%u\n", width, height, scale, renderer->render_width(), renderer->render_height());
 
         if (denoise)
             for (const auto& kv : {std::pair<const char*, double>{"denoise", (double)denoise}, {"denoise_temporal", 16.0}, {"denoise_motion", 1.0}})

@@ -537,16 +537,16 @@ void synchronize_system(Scene& scene, Backend& renderer)
     if (changed) renderer.synchronize(); // :203-205
 }
 
-void render_system(const Camera3D& camera, uint32_t width, uint32_t height, Backend& renderer)
+void render_system(const Camera3D& camera, uint32_t /*width*/, uint32_t /*height*/, Backend& renderer)
 {
-    const rfw_camera_view_3d view = camera.get_view(width, height);
+    const rfw_camera_view_3d view = camera.get_view(renderer.render_width(), renderer.render_height());
     renderer.render(mat4_identity(), view, RFW_RENDER_DEFAULT);
 }
 
-void render_system(const Camera3D& camera, const Camera2D& camera_2d, uint32_t width, uint32_t height, Backend& renderer)
+void render_system(const Camera3D& camera, const Camera2D& camera_2d, uint32_t /*width*/, uint32_t /*height*/, Backend& renderer)
 {
-    const rfw_camera_view_3d view = camera.get_view(width, height);
-    renderer.render(camera_2d.get_view(), view, RFW_RENDER_DEFAULT);
+    const rfw_camera_view_3d view = camera.get_view(renderer.render_width(), renderer.render_height());
+    renderer.render(camera_2d.get_view(), view, RFW_RENDER_DEFAULT); // (the 2D camera was made for the window: Camera2D::from_width_height)
 }
 
 // ------------------------------------------------------------------ the 2D layer's inputs
@@ -1463,8 +1463,19 @@ struct TableBackend : rfw::Backend {
         if (this->t.set_textures) acc(this->t.set_textures(this->t.instance, t.data(), (uint32_t)t.size(), nullptr));
     }
     void synchronize() override { acc(t.synchronize(t.instance)); }
-    void render(const rfw_mat4&, const rfw_camera_view_3d&, uint32_t) override {}
-    void resize(uint32_t, uint32_t, double) override {}
+    // render / resize are not in the table: the views render_system hands over and the sizes of the last resize are kept for the caller
+    // (rfwhost_render_system); the render size is the trait's (window * scale) truncated
+    uint32_t win_w = 0, win_h = 0, ren_w = 0, ren_h = 0, renders = 0;
+    rfw_mat4 last_view_2d{};
+    rfw_camera_view_3d last_view_3d{};
+    void render(const rfw_mat4& v2, const rfw_camera_view_3d& v3, uint32_t) override { last_view_2d = v2; last_view_3d = v3; renders++; }
+    void resize(uint32_t w, uint32_t h, double s) override
+    {
+        win_w = w; win_h = h;
+        ren_w = std::max(1u, (uint32_t)((double)w * s)); ren_h = std::max(1u, (uint32_t)((double)h * s));
+    }
+    uint32_t render_width() const override { return ren_w; }
+    uint32_t render_height() const override { return ren_h; }
     void set_point_lights(const std::vector<rfw_point_light>& l, const std::vector<uint32_t>*) override
     {
         acc(t.set_point_lights(t.instance, l.data(), (uint32_t)l.size(), nullptr));
@@ -1842,6 +1853,21 @@ HOST_API int rfwhost_synchronize(void* p, const rfwhost_backend_table* table)
     b.t = *table;
     rfw::synchronize_system(h.scene, b);
     return b.rc;
+}
+// runs rfw::render_system for a window of w x h under `scale` against a backend that only records: the 3D view and (with_2d) the 2D view
+// it was handed, the latter from Camera2D::from_width_height(w, h) as a host makes it
+HOST_API int rfwhost_render_system(void* p, uint32_t w, uint32_t h, double scale, int with_2d, rfw_camera_view_3d* view_3d_out, float* view_2d_out16)
+{
+    HostScene& hs = *(HostScene*)p;
+    TableBackend b;
+    std::memset(&b.t, 0, sizeof(b.t));
+    b.resize(w, h, scale);
+    if (with_2d) rfw::render_system(hs.cam, rfw::Camera2D::from_width_height(w, h), w, h, b);
+    else rfw::render_system(hs.cam, w, h, b);
+    if (b.renders != 1) return 1;
+    if (view_3d_out) *view_3d_out = b.last_view_3d;
+    if (view_2d_out16) std::memcpy(view_2d_out16, b.last_view_2d.m, sizeof(b.last_view_2d.m));
+    return 0;
 }
 HOST_API uint64_t rfwhost_triangle_count(void* p) { return ((HostScene*)p)->scene.triangle_count(); }
 HOST_API uint32_t rfwhost_counts(void* p, uint32_t what)

@@ -45,13 +45,18 @@ struct Backend {
     virtual void set_directional_lights(const std::vector<rfw_directional_light>& lights, const std::vector<uint32_t>* changed) = 0;
     virtual void set_skybox(const rfw_texture_data& skybox) = 0;
     virtual void set_skins(const std::vector<rfw_skin_data>& skins, const std::vector<uint32_t>* changed) = 0;
+    // not of the trait: the size the backend traces at under the scale of init / resize, (window * scale) truncated — what rfw's RenderSystem
+    // keeps as render_width() / render_height() (rfw/src/system/mod.rs:217-223) and asks the camera's view for
+    virtual uint32_t render_width() const = 0;
+    virtual uint32_t render_height() const = 0;
 };
 
 // The MI355X backend: every trait method forwards to the C entry point of the same name.
 // Trait methods return (); failures surface the way the reference's backends do (panic) — here a C++ exception.
 class HipBackend : public Backend {
 public:
-    // FromWindowHandle::init(window, width, height, scale) — headless: the window handle is ignored.
+    // FromWindowHandle::init(window, width, height, scale) — headless: the window handle is ignored; the frame is traced at
+    // (width * scale, height * scale) and presented at width x height (include/rfw_hip.h, rfw_hip_create).
     static HipBackend* init(uint32_t width, uint32_t height, double scale, const rfw_hip_options* options = nullptr)
     {
         if (rfw_hip_abi_version() != RFW_HIP_ABI_VERSION) throw std::runtime_error("librfw_hip.so was built from another version of include/rfw_hip.h");
@@ -82,6 +87,8 @@ public:
     void synchronize() override { check(rfw_hip_synchronize(inst_)); }
     void render(const rfw_mat4& v2, const rfw_camera_view_3d& v3, uint32_t mode) override { check(rfw_hip_render(inst_, &v2, &v3, mode)); }
     void resize(uint32_t w, uint32_t h, double s) override { check(rfw_hip_resize(inst_, w, h, s)); }
+    uint32_t render_width() const override { return render_size(0); }
+    uint32_t render_height() const override { return render_size(1); }
     void set_point_lights(const std::vector<rfw_point_light>& l, const std::vector<uint32_t>* ch) override
     {
         check(rfw_hip_set_point_lights(inst_, l.data(), (uint32_t)l.size(), ch ? ch->data() : nullptr));
@@ -109,6 +116,12 @@ private:
     void check(int rc) const
     {
         if (rc != RFW_HIP_OK) throw std::runtime_error(std::string("rfw_hip: ") + rfw_hip_last_error(inst_));
+    }
+    uint32_t render_size(int axis) const
+    {
+        uint32_t wh[2] = {0, 0};
+        check(rfw_hip_get_render_size(inst_, &wh[0], &wh[1]));
+        return wh[axis];
     }
     void* inst_;
 };
@@ -323,6 +336,8 @@ rfw_mat4 mat4_from_trs(const float t[3], const float axis[3], float angle, float
 // rfw/src/system/mod.rs:19-206
 void synchronize_system(Scene& scene, Backend& renderer);
 // rfw/src/lib.rs:411-430
+// width x height: the window.  The 3D view is the camera's for the backend's RENDER size (rfw/src/system/mod.rs:217-223 under a scale: the
+// spread angle follows the pixels that are traced); the 2D camera keeps the window size.
 void render_system(const Camera3D& camera, uint32_t width, uint32_t height, Backend& renderer);
 void render_system(const Camera3D& camera, const Camera2D& camera_2d, uint32_t width, uint32_t height, Backend& renderer); // with the 2D layer's view
 

@@ -40,6 +40,7 @@ def host_lib():
         l.rfwhost_set_aspect.argtypes = [C.c_void_p, C.c_float]
         l.rfwhost_camera_view.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pod.CameraView3D)]
         l.rfwhost_mark_all_changed.argtypes = [C.c_void_p]
+        l.rfwhost_render_system.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.POINTER(pod.CameraView3D), C.POINTER(C.c_float)]
         l.rfwhost_synchronize.argtypes = [C.c_void_p, C.POINTER(BackendTable)]
         l.rfwhost_triangle_count.argtypes = [C.c_void_p]
         l.rfwhost_triangle_count.restype = C.c_uint64
@@ -300,6 +301,15 @@ class Scene:
         v = pod.CameraView3D()
         self._l.rfwhost_camera_view(self._h, width, height, C.byref(v))
         return v
+
+    def render_system(self, width, height, scale=1.0, with_2d=False):
+        """rfw::render_system for a window of width x height under `scale`, against a backend that only records what it is handed: the 3D
+        view (the camera's for the RENDER size) and, with_2d, the 16 floats of the 2D view (Camera2D::from_width_height of the window)."""
+        import numpy as np
+        v, m = pod.CameraView3D(), np.zeros(16, np.float32)
+        if self._l.rfwhost_render_system(self._h, width, height, scale, int(with_2d), C.byref(v), m.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+            raise RuntimeError("rfwhost_render_system: the backend was not handed exactly one frame")
+        return (v, m) if with_2d else v
 
     def replace_mesh_with_sphere(self, mesh_id, sphere_no, seed, quality=4):
         """Mesh `mesh_id` becomes displaced sphere number `sphere_no` of the atrium (quality 4 = 5120 triangles); marked changed."""
