@@ -59,6 +59,8 @@ extern "C" {
     fn rfw_hip_host_free(ptr: *mut c_void);
     fn rfw_hip_download_frame(instance: *mut c_void, what: u32, frame: u32, host: *mut f32, n: u64) -> c_int;
     fn rfw_hip_wait_download(instance: *mut c_void, host: *const c_void) -> c_int;
+    fn rfw_hip_set_option(instance: *mut c_void, key: *const c_char, value: c_double) -> c_int;
+    fn rfw_hip_debug_read(instance: *mut c_void, what: *const c_char, dst: *mut c_void, bytes: u64, written: *mut u64) -> c_int;
 }
 
 pub struct HipBackend { instance: *mut c_void }
@@ -90,6 +92,19 @@ impl HipBackend {
     /// every rank (tiles traced locally, one RCCL all-gather per frame on the backend's own HIP stream).
     pub fn comm_unique_id() -> [u8; 128] { let mut id = [0u8; 128]; assert_eq!(unsafe { rfw_hip_comm_unique_id(id.as_mut_ptr()) }, 0); id }
     pub fn comm_init(&self, id: &[u8; 128], rank: u32, world: u32) { self.check(unsafe { rfw_hip_comm_init(self.instance, id.as_ptr(), rank, world) }) }
+    /// Extension: an option of include/rfw_hip.h (the trait has none), e.g. the display transform: `set_option("tonemap", 3.0)`,
+    /// `set_option("auto_exposure", 1.0)`, `set_option("exposure", 2.0)`.  A refused key or value panics with the library's message.
+    pub fn set_option(&self, key: &str, value: f64) {
+        let key = std::ffi::CString::new(key).expect("option keys hold no NUL");
+        self.check(unsafe { rfw_hip_set_option(self.instance, key.as_ptr(), value) })
+    }
+    /// The exposure the display transform applied to the latest transformed frame and the target it adapts towards (option "tonemap");
+    /// None before the first such frame.
+    pub fn display_exposure(&self) -> Option<(f32, f32)> {
+        let (mut state, mut written) = ([0f32; 4], 0u64);
+        self.check(unsafe { rfw_hip_debug_read(self.instance, b"display_state\0".as_ptr() as *const c_char, state.as_mut_ptr() as *mut c_void, 16, &mut written) });
+        if written == 16 { Some((state[0], state[1])) } else { None }
+    }
     /// Extension: the tonemapped frame (the trait itself has no read-back).
     pub fn read_framebuffer(&self, rgba: &mut [f32]) { self.check(unsafe { rfw_hip_read_framebuffer(self.instance, rgba.as_mut_ptr(), rgba.len() as u64) }) }
     /// Queue the copy of the frame just rendered, as B,G,R,A bytes, into a pinned buffer from `rfw_hip_host_alloc(width * height * 4)`;

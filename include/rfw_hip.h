@@ -252,6 +252,28 @@ RFW_HIP_API int rfw_hip_synchronize(void* instance);
  * world > 1 or any exchange of tiles (the guides stay on their ranks: the frame finalises unfiltered, as FILTERED_SSAO finalises as SSAO
  * there); modes 1-6 ignore the option.  Setting either option to a different value restarts accumulation.  The filter assumes a finite
  * accumulator ("clamp_value"); a NaN or Inf pixel is skipped as a tap and spoils only itself.
+ * Option "tonemap" = 0 (off, the default) | 1 exposure only | 2 extended Reinhard | 3 ACES fit (Narkowicz): the display transform (DESIGN.md
+ * "Display transform").  Where "denoise" would act — DEFAULT frames of rfw_hip_render and rfw_hip_render_samples, every frame slot, with
+ * sub-streams, world <= 1 and no exchange of tiles — the finalised frame is transformed in place at the render size, directly behind the
+ * finaliser (the a-trous filter included) and before the render scale and the 2D layer, which the curve never touches.  Only the finished
+ * frame changes (read_framebuffer*, download_frame what = 0 and 2): the accumulator and the denoiser's history never see it; modes 1-6,
+ * rfw_hip_render_batch and exchanged or sharded frames finalise as without it.  With 0 nothing is launched or allocated and every frame is
+ * what it is without the option.  The frame is gamma-2 (sqrt(acc / samples)); per pixel c, w copied, in single uncontracted float32
+ * operations with the correctly rounded division and square root:
+ *   lin = c * c per channel; v = lin * E; out = sqrt(m) with
+ *   1: m = v    2: t = v / (W * W); t = 1 + t; n = v * t; dd = 1 + v; m = n / dd    (W = "tonemap_white", finite, > 0, default 4)
+ *   3: n = 2.51 v; n = n + 0.03; n = v * n; dd = 2.43 v; dd = dd + 0.59; dd = v * dd; dd = dd + 0.14; m = n / dd clamped to [0, 1] (a NaN stays)
+ * E is "exposure" (finite, 2^-20 ... 2^20, default 1), or with "auto_exposure" = 1 (default 0) the adapted exposure of the frame: a histogram
+ * of Y = 0.2126 r + 0.7152 g + 0.0722 b (of lin, summed left to right) in 256 bins of 1/8 octave over [2^-16, 2^16) — a pixel counts iff
+ * Y >= 2^-16, its bin is min(255, (bits(Y) >> 20) - 888) — resolved in integers: N = sum c[k], lo = N low / 100, hi = N high / 100 ("exposure_low",
+ * "exposure_high": integer percent, 0 <= low < high <= 100, default 50 and 95), S = sum k max(0, min(cum_k + c[k], hi) - max(cum_k, lo)) with
+ * cum the exclusive prefix, C = hi - lo, q = 256 S / C, Lfix = ((q + 128) << 12) - (16 << 23), e = bits(1.0f) + ((int32)bits(key) - bits(1.0f)) - Lfix
+ * ("exposure_key": 2^-10 ... 2^10, default 0.18) clamped as an integer to [bits(min), bits(max)] ("exposure_min" <= "exposure_max", both
+ * 2^-20 ... 2^20, default 1/64 and 64), E* = as_float(e); C == 0: E* = the previous exposure, or 1.  Without a previous exposure E = E*, else
+ * d = E* - Eprev; d = d * speed; E = Eprev + d ("exposure_speed": (0, 1], per frame, default 0.125).  The state is one device record per
+ * instance, used by successive calls in call order whatever the frame slot, with no host wait or read-back.  Any other value of these
+ * options is RFW_HIP_E_INVALID.  A change applies from the next frame and never restarts accumulation; setting any of them, and
+ * rfw_hip_resize, drops the adaptation state; rfw_hip_reset_accumulation and a new image keep it.
  * Option "sample_offset" = s (an integer 0 ... 2^24, default 0): the samples of every image take the indices s, s + 1, ... for their seeds
  * and the blue-noise sequence, while the sample COUNT (the frame's divisor, rfw_hip_frame_stats.sample_count) still starts at 0; modes 1-6
  * honour it, rfw_hip_render_batch keeps index 0.  A different value starts a new image.
@@ -310,7 +332,9 @@ RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
  *                  "denoise_temporal" 0 (off, default) | 1 ... 64 samples of history across images, "denoise_motion" 0 (off, default) | 1
  *                  the history follows moving instances, "sample_offset" 0 (default) ... 2^24, the first sample index of every
  *                  image — any other value of these is RFW_HIP_E_INVALID; see rfw_hip_render; "scale_filter" 0 nearest | 1 (default)
-                  bilinear / area: how the render-size frame becomes the window-size one (see rfw_hip_create)
+                  bilinear / area: how the render-size frame becomes the window-size one (see rfw_hip_create); the display transform:
+ *                  "tonemap" 0 (off, default) | 1 | 2 | 3, "exposure", "tonemap_white", "auto_exposure" 0 | 1, "exposure_key",
+ *                  "exposure_min" / "exposure_max", "exposure_low" / "exposure_high", "exposure_speed" (see rfw_hip_render)
  *   measurement    "count_traversal" (node / triangle / instance counters of the next frames), "timing" (HIP events per kernel),
  *                  "denoise_form" 0 | 1 | 2 (the a-trous kernel form: the faster one per step | direct | tiled; the image is the same)
  *   ray order      "shadow_order" 0 | 1 | 2 (which end any-hit traversals start from; the image is the same under every order),
@@ -440,7 +464,10 @@ RFW_HIP_API int rfw_hip_occludes4(void* instance, const float* origin_xyz4, cons
  * snapped vertices, 8 sub-pixel bits, in the caller's vertex order; 0 where a vertex had no pixel position: w <= 0, not finite, too far), uint32 mesh, instance, triangle,
  * dropped (0 or 1), two pad words; nothing when the latest frame drew no 2D layer.  "ov_stats": three uint32 of that frame: primitives
  * drawn, primitives dropped, bin words written.  With frame slots both taps follow the slot of the latest frame, like the other per-frame
- * taps. */
+ * taps.
+ * "display_state" (option "tonemap"): 16 bytes of the latest transformed frame, whichever slot ran it: float E applied, float E*, uint32 q,
+ * uint32 N (manual exposure: E, E, 0, 0); nothing before the first such frame, and nothing once the adaptation state has been dropped.
+ * "display_hist": the 256 uint32 counts that frame's exposure was resolved from (automatic exposure only). */
 RFW_HIP_API int rfw_hip_debug_read(void* instance, const char* what, void* dst, uint64_t bytes, uint64_t* written);
 
 /* occludes() that also reports how many 4-wide nodes each any-hit traversal visited (the any-hit counterpart of rfw_hip_depth_test).  For
@@ -462,6 +489,13 @@ RFW_HIP_API int rfw_hip_debug_lbvh_stress(void* instance, uint32_t num_boxes, ui
  * (synchronize first) -> P.xyz, pickProb, lightPdf, colour.rgb, picked light (shade.comp:413-528); 5: RandomBarycentrics(r0 = [41]) -> barycentrics
  * (shade.comp:371-411). */
 RFW_HIP_API int rfw_hip_debug_eval_shading(void* instance, int op, uint64_t n, const float* in48, float* out12);
+
+/* Test-only: the display transform (option "tonemap", see rfw_hip_render) on a caller-supplied frame of w x h float4 pixels — the very
+ * launches a frame issues, under the instance's current options, on a scratch copy.  prev_exposure <= 0: there is no previous exposure.
+ * frame_out: w * h * 4 floats; hist256 (nullable): the 256 counts resolved from (zeros without automatic exposure); state4 (nullable): E
+ * applied, E*, q, N as in "display_state" (zeros with "tonemap" 0).  The instance's adaptation state and frames are neither read nor written. */
+RFW_HIP_API int rfw_hip_debug_display(void* instance, const float* frame_in, uint32_t w, uint32_t h, float prev_exposure, float* frame_out,
+                                      uint32_t* hist256, float* state4);
 
 /* A batch of `count` independent NEW images, one per view, traced as one tall virtual frame: every stage of the wavefront loop is ONE
  * launch over the paths of all frames (bigger launches, fewer of them; with a sharded frame also ONE all-gather per batch).  Each

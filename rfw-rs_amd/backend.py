@@ -26,7 +26,7 @@ EXPORTS = [
     "rfw_hip_shard_info", "rfw_hip_set_slab_output", "rfw_hip_assemble_frame", "rfw_hip_intersect", "rfw_hip_occludes", "rfw_hip_debug_occludes_depth",
     "rfw_hip_debug_read", "rfw_hip_bandwidth_probe", "rfw_hip_depth_test", "rfw_hip_render_batch", "rfw_hip_assemble_batch",
     "rfw_hip_read_framebuffer_at", "rfw_hip_read_accumulator_at", "rfw_hip_host_alloc", "rfw_hip_host_free", "rfw_hip_download_frame",
-    "rfw_hip_wait_downloads", "rfw_hip_wait_download", "rfw_hip_srgb_steps", "rfw_hip_render_samples", "rfw_hip_set_blue_noise", "rfw_hip_debug_eval_shading", "rfw_hip_comm_unique_id", "rfw_hip_comm_init", "rfw_hip_comm_init_loopback", "rfw_hip_comm_destroy", "rfw_hip_p2p_export", "rfw_hip_p2p_connect", "rfw_hip_p2p_disconnect", "rfw_hip_intersect4", "rfw_hip_occludes4", "rfw_hip_debug_lbvh_stress", "rfw_hip_issue_probe", "rfw_hip_get_render_size",
+    "rfw_hip_wait_downloads", "rfw_hip_wait_download", "rfw_hip_srgb_steps", "rfw_hip_render_samples", "rfw_hip_set_blue_noise", "rfw_hip_debug_eval_shading", "rfw_hip_comm_unique_id", "rfw_hip_comm_init", "rfw_hip_comm_init_loopback", "rfw_hip_comm_destroy", "rfw_hip_p2p_export", "rfw_hip_p2p_connect", "rfw_hip_p2p_disconnect", "rfw_hip_intersect4", "rfw_hip_occludes4", "rfw_hip_debug_lbvh_stress", "rfw_hip_issue_probe", "rfw_hip_get_render_size", "rfw_hip_debug_display",
 ]
 
 _lib = None
@@ -101,6 +101,7 @@ def hip_lib():
         l.rfw_hip_render_samples.argtypes = [vp, C.POINTER(pod.CameraView3D), C.c_uint32]
         l.rfw_hip_set_blue_noise.argtypes = [vp, vp, C.c_uint32]
         l.rfw_hip_debug_eval_shading.argtypes = [vp, C.c_int, u64, vp, vp]
+        l.rfw_hip_debug_display.argtypes = [vp, vp, u32, u32, f32, vp, vp, vp]
         l.rfw_hip_comm_unique_id.argtypes = [vp]
         l.rfw_hip_comm_init.argtypes = [vp, vp, u32, u32]
         l.rfw_hip_comm_destroy.argtypes = [vp]
@@ -334,6 +335,31 @@ class HipBackend:
         out = np.zeros((len(a), 12), dtype=np.float32)
         self._check(self._l.rfw_hip_debug_eval_shading(self._h, op, len(a), a.ctypes.data, out.ctypes.data))
         return out
+
+    def debug_display(self, frame, prev_exposure=0.0):
+        """Test-only: the display transform (option "tonemap") under the current options on a caller-supplied (H, W, 4) float32 frame;
+        prev_exposure <= 0: no previous exposure.  Returns (frame (H, W, 4), the 256 counts, state) with state as display_state()."""
+        a = np.ascontiguousarray(frame, dtype=np.float32)
+        h, w = a.shape[:2]
+        out, hist, state = np.empty_like(a), np.zeros(256, np.uint32), np.zeros(4, np.float32)
+        self._check(self._l.rfw_hip_debug_display(self._h, a.ctypes.data, w, h, prev_exposure, out.ctypes.data, hist.ctypes.data, state.ctypes.data))
+        return out, hist, self._display_state(state.tobytes())
+
+    @staticmethod
+    def _display_state(raw):
+        f, u = np.frombuffer(raw, np.float32), np.frombuffer(raw, np.uint32)
+        return {"exposure": f[0], "target": f[1], "q": int(u[2]), "n": int(u[3])}
+
+    def display_state(self):
+        """What the display transform (option "tonemap") applied to the latest transformed frame: the exposure E, the target E* it adapts
+        towards, and q and N of the histogram's resolve (manual exposure: E, E, 0, 0); None before the first such frame and after the
+        adaptation state was dropped."""
+        raw = self.debug_read("display_state", 16).tobytes()
+        return self._display_state(raw) if len(raw) == 16 else None
+
+    def display_histogram(self):
+        """The 256 counts the latest frame's automatic exposure was resolved from; empty without such a frame."""
+        return np.frombuffer(self.debug_read("display_hist", 1024).tobytes(), np.uint32).copy()
 
     @staticmethod
     def comm_unique_id():

@@ -297,6 +297,9 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         for (int q = 0; q < 2; q++) HIP_TRY(I, O->d_dn_history[q].ensure(3 * px));
         if (!O->dn_chain) HIP_TRY(I, hipEventCreateWithFlags(&O->dn_chain, hipEventDisableTiming));
     }
+    // option "tonemap": the display transform acts on the finished frame of a path-traced image where the frame is de-tiled on this device
+    // and the call leaves ONE image behind (as "denoise"); off: no launch, no allocation
+    const bool disp = O->display.curve > 0 && mode == RFW_HIP_RENDER_DEFAULT && (k == 1 || samples) && I->world <= 1 && !O->comm && !O->loop && !O->p2p.connected;
     // option "denoise_motion": acts where the temporal option does
     const bool dnm = dnt && O->denoise_motion > 0;
     if (dnm) {
@@ -505,6 +508,31 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         else if (mode == RFW_HIP_RENDER_FILTERED_SSAO) launch_ao_filter(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_ao_guide.ptr, I->d_frame_out.ptr, I->sample_count);
         else launch_assemble(main, cam[0], I->d_acc_slab.ptr, false, false, I->cap_v, I->d_frame_out.ptr, I->sample_count, mode != RFW_HIP_RENDER_DEFAULT);
         I->acc_source = I->d_acc_slab.ptr; I->acc_source_rgb = false; I->acc_source_batch = frames_out;
+        if (disp) { // the display transform, in place at the render size: the accumulator and the denoiser's history never see it
+            const uint64_t px = (uint64_t)I->width * I->height;
+            if (O->display.automatic) {
+                if (!I->d_disp_hist.ptr) { // the 256 words this slot's frames count into: zeroed once, every resolve leaves them zero
+                    HIP_TRY(I, I->d_disp_hist.ensure(kDisplayHistWords));
+                    HIP_TRY(I, hipMemsetAsync(I->d_disp_hist.ptr, 0, kDisplayHistWords * sizeof(uint32_t), main));
+                }
+                HIP_TRY(I, O->d_disp_state.ensure(kDisplayStateWords + 256u));
+                if (!O->disp_chain) HIP_TRY(I, hipEventCreateWithFlags(&O->disp_chain, hipEventDisableTiming));
+                float* const frame_e = reinterpret_cast<float*>(I->d_disp_hist.ptr + 256);
+                launch_display_hist(main, I->d_frame_out.ptr, px, I->d_disp_hist.ptr);
+                // behind the resolve of the frame before, in call order: it wrote the record this one reads
+                if (O->disp_chain_pending) HIP_TRY(I, hipStreamWaitEvent(main, O->disp_chain, 0));
+                launch_display_resolve(main, O->display, O->disp_have_state, I->d_disp_hist.ptr, O->d_disp_state.ptr, frame_e, O->d_disp_state.ptr + kDisplayStateWords);
+                HIP_TRY(I, hipEventRecord(O->disp_chain, main));
+                O->disp_chain_pending = true;
+                O->disp_have_state = true;
+                O->disp_latest = 2u;
+                launch_display_apply(main, O->display, frame_e, I->d_frame_out.ptr, px);
+            } else {
+                launch_display_apply(main, O->display, nullptr, I->d_frame_out.ptr, px);
+                O->disp_latest = 1u;
+                O->disp_manual = O->display.exposure;
+            }
+        }
         if (scaled(I)) // the render scale: every frame this call leaves behind -> the window size; from here on the window frame is THE frame
             launch_resample(main, I->d_frame_out.ptr, I->width, I->height, I->d_frame_win.ptr, I->window_w, I->window_h, O->scale_filter, frames_out);
         if (ov) { // the 2D layer, in place over the frame the finaliser just wrote (behind the history's event: the history never sees it)
@@ -745,6 +773,8 @@ void rfw_hip_destroy(void* inst)
         I->d_dn_ids.release(); I->d_dn_motion.release();
         for (int q = 0; q < 2; q++) { I->d_dn_history_ids[q].release(); I->d_dn_snapshot[q].release(); }
         if (I->dn_chain) (void)hipEventDestroy(I->dn_chain);
+        I->d_disp_state.release(); I->d_disp_hist.release();
+        if (I->disp_chain) (void)hipEventDestroy(I->disp_chain);
         release_overlay(I);
         for (auto& ev : I->ring)
             if (ev) (void)hipEventDestroy(ev);
@@ -860,6 +890,7 @@ int rfw_hip_resize(void* inst, uint32_t w, uint32_t h, double scale)
     I->d_dn_ids.release(); I->d_dn_motion.release();
     for (int q = 0; q < 2; q++) { I->d_dn_history_ids[q].release(); I->d_dn_snapshot[q].release(); I->dn_snap_count[q] = 0; }
     I->dn_motion_count = 0;
+    I->disp_have_state = false; I->disp_latest = 0; // the display transform adapted to frames of the old size
     I->ov_frame_prims = I->ov_frame_words = 0; // the 2D layer's taps describe a frame of the old size
     // a gathered frame not de-tiled yet belongs to the old size (and d_recv may move below): forget it (each slot passes here for itself)
     I->deferred = Instance::Deferred(); I->acc_source = nullptr; I->presented_valid = false;
@@ -969,6 +1000,47 @@ int rfw_hip_set_option(void* inst, const char* key, double value)
     else if (k == "scale_filter") { // how the render-size frame becomes the window-size one (resample.inc): 0 nearest, 1 bilinear / area; from the next frame on, the image goes on
         if (value != 0.0 && value != 1.0) return fail(I, RFW_HIP_E_INVALID, "set_option: scale_filter is 0 (nearest) or 1 (bilinear / area)");
         I->scale_filter = (uint32_t)value;
+    }
+    else if (k == "tonemap" || k == "exposure" || k == "tonemap_white" || k == "auto_exposure" || k == "exposure_key" || k == "exposure_min" || k == "exposure_max" ||
+             k == "exposure_low" || k == "exposure_high" || k == "exposure_speed") {
+        // the display transform (display.inc): from the next frame on, the image goes on; any of them drops the adaptation state
+        DisplayParams& d = I->display;
+        const float f = (float)value;
+        const bool integer = std::isfinite(value) && value == std::floor(value);
+        auto within = [&](float lo, float hi) { return std::isfinite(value) && value >= (double)lo && value <= (double)hi && f >= lo && f <= hi; };
+        if (k == "tonemap") {
+            if (!integer || value < 0.0 || value > 3.0) return fail(I, RFW_HIP_E_INVALID, "set_option: tonemap is 0 (off), 1 (exposure only), 2 (extended Reinhard) or 3 (ACES fit)");
+            d.curve = (uint32_t)value;
+        } else if (k == "exposure") {
+            if (!within(0x1p-20f, 0x1p20f)) return fail(I, RFW_HIP_E_INVALID, "set_option: exposure is 2^-20 ... 2^20");
+            d.exposure = f;
+        } else if (k == "tonemap_white") {
+            if (!std::isfinite(value) || !(value > 0.0) || !(f > 0.0f) || !std::isfinite(f)) return fail(I, RFW_HIP_E_INVALID, "set_option: tonemap_white is finite and > 0");
+            d.white = f;
+        } else if (k == "auto_exposure") {
+            if (value != 0.0 && value != 1.0) return fail(I, RFW_HIP_E_INVALID, "set_option: auto_exposure is 0 or 1");
+            d.automatic = (uint32_t)value;
+        } else if (k == "exposure_key") {
+            if (!within(0x1p-10f, 0x1p10f)) return fail(I, RFW_HIP_E_INVALID, "set_option: exposure_key is 2^-10 ... 2^10");
+            d.key = f;
+        } else if (k == "exposure_min") {
+            if (!within(0x1p-20f, d.exposure_max)) return fail(I, RFW_HIP_E_INVALID, "set_option: exposure_min is 2^-20 ... exposure_max");
+            d.exposure_min = f;
+        } else if (k == "exposure_max") {
+            if (!within(d.exposure_min, 0x1p20f)) return fail(I, RFW_HIP_E_INVALID, "set_option: exposure_max is exposure_min ... 2^20");
+            d.exposure_max = f;
+        } else if (k == "exposure_low") {
+            if (!integer || value < 0.0 || !(value < (double)d.high)) return fail(I, RFW_HIP_E_INVALID, "set_option: exposure_low is an integer percentage, 0 <= low < exposure_high");
+            d.low = (uint32_t)value;
+        } else if (k == "exposure_high") {
+            if (!integer || !(value > (double)d.low) || value > 100.0) return fail(I, RFW_HIP_E_INVALID, "set_option: exposure_high is an integer percentage, exposure_low < high <= 100");
+            d.high = (uint32_t)value;
+        } else {
+            if (!std::isfinite(value) || !(value > 0.0) || value > 1.0 || !(f > 0.0f)) return fail(I, RFW_HIP_E_INVALID, "set_option: exposure_speed is in (0, 1]");
+            d.speed = f;
+        }
+        I->disp_have_state = false;
+        I->disp_latest = 0;
     }
     else if (k == "gather_format") { // 0 f32 accumulator RGB, 1 f16 finished frame, 2 presented BGRA8 (sharded frames only)
         if (value < 0 || value > 2) return fail(I, RFW_HIP_E_INVALID, "set_option: gather_format is 0, 1 or 2");

@@ -513,6 +513,19 @@ struct Instance {
     DevBuf<uint32_t> d_dn_history_ids[2];
     DevBuf<char> d_dn_snapshot[2], d_dn_motion;
     uint32_t dn_snap_count[2] = {}, dn_motion_count = 0;
+    // The display transform (owner; DESIGN.md "Display transform"): the options, the adaptation state — one device record (E, E*, q, N)
+    // followed by the 256 counts the latest frame resolved from, allocated at the first frame with automatic exposure — and whether a
+    // frame has written it since it was last dropped.  The resolve stages of successive frames are chained through disp_chain, whichever
+    // slots' streams they run on.  disp_latest: what "display_state" reports (0 nothing, 1 the manual exposure disp_manual, 2 the record).
+    // Per slot: the 256 words its frames count into (zero between frames) and, behind them, its latest frame's own copy of E.
+    DisplayParams display;
+    DevBuf<uint32_t> d_disp_state;
+    bool disp_have_state = false;
+    uint32_t disp_latest = 0;
+    float disp_manual = 1.0f;
+    hipEvent_t disp_chain = nullptr;
+    bool disp_chain_pending = false;
+    DevBuf<uint32_t> d_disp_hist;
     // The 2D layer (DESIGN.md "2D layer").  Owner: the host copies of set_2d_mesh / set_2d_instances; synchronize() flattens them into the
     // draws of a frame (mesh id, then instance index) and writes them as a NEW version of two small device arrays on the upload stream, the
     // way the material and light tables are versioned: frames in flight keep the version they started with and nothing waits for them.

@@ -239,7 +239,8 @@ int rfw_hip_debug_lbvh_stress(void* inst, uint32_t n, uint32_t iterations, uint3
 // what: "hit0"/"hit1" (uint4), "ray_o0"/"ray_o1", "ray_d0"/"ray_d1", "thr0"/"thr1", "sh_o", "sh_d", "sh_e" (float4), "counters",
 //       "xforms" (InstanceXform), "normals" (InstanceNormal), "ao_rays", "ao_guide" (render modes 5, 6: DESIGN.md "Render modes"),
 //       "dn_guide" (option "denoise": DESIGN.md "Denoiser"), "dn_history" (option "denoise_temporal": DESIGN.md "Denoiser: temporal"),
-//       "dn_ids", "dn_motion" (option "denoise_motion": DESIGN.md "Denoiser: motion"), "ov_prims", "ov_stats" (DESIGN.md "2D layer")
+//       "dn_ids", "dn_motion" (option "denoise_motion": DESIGN.md "Denoiser: motion"), "ov_prims", "ov_stats" (DESIGN.md "2D layer"),
+//       "display_state", "display_hist" (option "tonemap": DESIGN.md "Display transform")
 int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, uint64_t* written)
 {
     LOCK(inst);
@@ -268,6 +269,24 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
         HIP_TRY(I, hipStreamSynchronize(I->stream));
         for (Instance* c : I->slots) HIP_TRY(I, hipStreamSynchronize(c->stream));
         if (n) HIP_TRY(I, hipMemcpy(dst, I->d_dn_motion.ptr, n, hipMemcpyDeviceToHost));
+        if (written) *written = n;
+        return RFW_HIP_OK;
+    }
+    if (w == "display_state" || w == "display_hist") { // owner state: what the display transform applied to the latest transformed frame, whichever slot ran it
+        uint32_t v[kDisplayStateWords + 256u] = {};
+        uint64_t avail = 0;
+        if (I->disp_latest == 2u && I->d_disp_state.ptr) {
+            HIP_TRY(I, hipStreamSynchronize(I->stream));
+            for (Instance* c : I->slots) HIP_TRY(I, hipStreamSynchronize(c->stream));
+            HIP_TRY(I, hipMemcpy(v, I->d_disp_state.ptr, sizeof(v), hipMemcpyDeviceToHost));
+            avail = w == "display_state" ? kDisplayStateWords * 4u : 256u * 4u;
+        } else if (I->disp_latest == 1u && w == "display_state") { // manual exposure: E = E*, nothing was counted
+            std::memcpy(&v[0], &I->disp_manual, 4);
+            std::memcpy(&v[1], &I->disp_manual, 4);
+            avail = kDisplayStateWords * 4u;
+        }
+        const uint64_t n = std::min<uint64_t>(bytes, avail);
+        if (n) std::memcpy(dst, w == "display_state" ? v : v + kDisplayStateWords, n);
         if (written) *written = n;
         return RFW_HIP_OK;
     }
@@ -382,6 +401,53 @@ int rfw_hip_debug_eval_shading(void* inst, int op, uint64_t n, const float* in48
     HIP_TRY(I, hipGetLastError());
     if (n) HIP_TRY(I, hipMemcpyAsync(out12, I->d_q_d.ptr, 12 * n * sizeof(float), hipMemcpyDeviceToHost, I->stream));
     HIP_TRY(I, hipStreamSynchronize(I->stream));
+    return RFW_HIP_OK;
+}
+
+// The display transform's launches (do_render) under the instance's current options on a scratch copy of a caller-supplied frame (tests
+// only): the instance's adaptation state and frames are neither read nor written
+int rfw_hip_debug_display(void* inst, const float* frame_in, uint32_t w, uint32_t h, float prev_exposure, float* frame_out, uint32_t* hist256, float* state4)
+{
+    LOCK(inst);
+    const uint64_t px = (uint64_t)w * h;
+    if (!frame_in || !frame_out || !w || !h || px > (1ull << 28)) return fail(I, RFW_HIP_E_INVALID, "debug_display: bad arguments");
+    HIP_TRY(I, hipSetDevice(I->device));
+    const DisplayParams& d = I->display;
+    const bool has_prev = prev_exposure > 0.0f;
+    uint32_t host[kDisplayHistWords + kDisplayStateWords + 256u] = {}; // a slot's words, then an owner's
+    if (has_prev) std::memcpy(&host[kDisplayHistWords], &prev_exposure, 4);
+    float4* frame = nullptr;
+    uint32_t* words = nullptr;
+    hipError_t e = hipMalloc((void**)&frame, px * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc((void**)&words, sizeof(host));
+    if (e == hipSuccess) e = hipMemcpyAsync(frame, frame_in, px * sizeof(float4), hipMemcpyHostToDevice, I->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(words, host, sizeof(host), hipMemcpyHostToDevice, I->stream);
+    if (e == hipSuccess && d.curve > 0u) {
+        uint32_t* const state = words + kDisplayHistWords;
+        float* const frame_e = reinterpret_cast<float*>(words + 256);
+        if (d.automatic) {
+            launch_display_hist(I->stream, frame, px, words);
+            launch_display_resolve(I->stream, d, has_prev, words, state, frame_e, state + kDisplayStateWords);
+            launch_display_apply(I->stream, d, frame_e, frame, px);
+        } else {
+            launch_display_apply(I->stream, d, nullptr, frame, px);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(frame_out, frame, px * sizeof(float4), hipMemcpyDeviceToHost, I->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(host, words, sizeof(host), hipMemcpyDeviceToHost, I->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(I->stream);
+    if (frame) (void)hipFree(frame);
+    if (words) (void)hipFree(words);
+    if (e != hipSuccess) return fail(I, RFW_HIP_E_DEVICE, std::string("debug_display: ") + hipGetErrorString(e));
+    if (d.curve > 0u && !d.automatic) { // manual exposure: E = E*, nothing was counted
+        std::memcpy(&host[kDisplayHistWords], &d.exposure, 4);
+        std::memcpy(&host[kDisplayHistWords + 1u], &d.exposure, 4);
+    } else if (d.curve == 0u) {
+        host[kDisplayHistWords] = 0u;
+    }
+    if (hist256) std::memcpy(hist256, host + kDisplayHistWords + kDisplayStateWords, 256u * 4u);
+    if (state4) std::memcpy(state4, host + kDisplayHistWords, kDisplayStateWords * 4u);
     return RFW_HIP_OK;
 }
 

@@ -188,6 +188,26 @@ void launch_overlay(hipStream_t s, const OvFrame& f, const rfw_vertex_2d* vertic
 // The render scale (resample.inc, DESIGN.md "Render scale"): `frames` finalised frames of rw x rh at `src` -> frames of w x h at `dst`; filter 0 =
 // nearest, 1 = bilinear when enlarging / exact area average when shrinking (per axis).  Issued only where the two sizes differ.
 void launch_resample(hipStream_t s, const float4* src, uint32_t rw, uint32_t rh, float4* dst, uint32_t w, uint32_t h, uint32_t filter, uint32_t frames);
+// The display transform (display.inc, DESIGN.md "Display transform"): exposure and a tone-map curve over a finalised mode-0 frame of n pixels,
+// in place, behind the finaliser and before the render scale and the 2D layer.  Manual exposure: launch_display_apply alone (frame_e null).
+// Automatic: hist (into 256 zeroed words), resolve
+// (one workgroup: the owner's record `state` = (E, E*, q, N) from the counts and the record before, this frame's E into *frame_e, the
+// counts into hist_copy, the 256 words zeroed again), apply (frame_e = what resolve wrote).
+struct DisplayParams {
+    uint32_t curve = 0;         // option "tonemap": 0 off, 1 exposure only, 2 extended Reinhard, 3 ACES fit
+    float exposure = 1.0f;      // "exposure"
+    float white = 4.0f;         // "tonemap_white"
+    uint32_t automatic = 0;     // "auto_exposure"
+    float key = 0.18f;          // "exposure_key"
+    float exposure_min = 1.0f / 64.0f, exposure_max = 64.0f;
+    uint32_t low = 50, high = 95; // "exposure_low", "exposure_high": percent
+    float speed = 0.125f;       // "exposure_speed"
+};
+constexpr uint32_t kDisplayStateWords = 4;      // the owner's record; the 256 counts it was resolved from follow it
+constexpr uint32_t kDisplayHistWords = 256 + 4; // a slot's histogram, then its latest frame's E
+void launch_display_hist(hipStream_t s, const float4* frame, uint64_t n, uint32_t* hist);
+void launch_display_resolve(hipStream_t s, const DisplayParams& d, bool has_prev, uint32_t* hist, uint32_t* state, float* frame_e, uint32_t* hist_copy);
+void launch_display_apply(hipStream_t s, const DisplayParams& d, const float* frame_e, float4* frame, uint64_t n);
 void launch_eval_shading(hipStream_t s, const SceneDev& sc, const CameraParams& cam, int op, uint32_t n, const float* in, float* out);
 void launch_query_closest(hipStream_t s, const SceneDev& sc, const float* origins, const float* directions, float t_min, float t_max, uint64_t n,
                           rfw_hip_hit* hits, uint32_t* depth = nullptr /* optional: nodes visited per ray */);

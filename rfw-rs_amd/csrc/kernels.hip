@@ -1523,5 +1523,7 @@ void launch_query_any(hipStream_t s, const SceneDev& sc, const float* origins, c
 #include "overlay.inc"
 // ---------------------------------------------------------------- the render scale: render-size frame -> window-size frame
 #include "resample.inc"
+// ---------------------------------------------------------------- the display transform: exposure, automatic exposure, tone-map curves
+#include "display.inc"
 
 } // namespace rfwhip

@@ -8,10 +8,13 @@
 // Where the reference presents to a window, this program downloads the presented (Bgra8UnormSrgb) frame of every frame into a ring of
 // pinned host buffers without stalling the frames in flight, and writes the last one as a PPM image.
 //
-//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--scale S] [--hud] [--out last.ppm]
+//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--scale S] [--tonemap K [--auto-exposure]] [--hud] [--out last.ppm]
 //
 // --denoise K (off by default) finalises every frame with K a-trous passes and a history of 16 samples that follows the bouncing
 // instances (options "denoise", "denoise_temporal", "denoise_motion"): every frame here is a new image of one sample per pixel.
+// --tonemap K (off by default) passes every frame through the display transform (option "tonemap": 1 exposure only, 2 extended Reinhard,
+// 3 ACES fit), --auto-exposure adapts the exposure to the frames' luminance from frame to frame (option "auto_exposure"); the exposure the
+// last frame was shown with is printed.
 // --hud (off by default) draws the frame counter and the frame time over the image the way rfw-font draws the reference's FPS counter: one
 // atlas texture (white, the glyphs in alpha, one mip level), one 2D mesh of glyph quads rewritten every frame, one 2D instance with the
 // pixel-space matrix, and the frame's Camera2D view (line 1: "frame N", line 2: "T ms" of the frame before).
@@ -30,8 +33,8 @@ int main(int argc, char** argv)
 {
     std::string gltf, out = "example_animated.ppm";
     std::vector<std::string> actors;
-    uint32_t frames = 240, width = 1280, height = 720, nx = 100, nz = 100, path_length = 2, denoise = 0;
-    bool hud = false;
+    uint32_t frames = 240, width = 1280, height = 720, nx = 100, nz = 100, path_length = 2, denoise = 0, tonemap = 0;
+    bool hud = false, auto_exposure = false;
     double scale = 1.0; // rfw's Settings::scale_mode = Custom(S): traced at size x S, presented at size
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -44,6 +47,8 @@ int main(int argc, char** argv)
         else if (a == "--path-length") path_length = (uint32_t)std::atoi(next());
         else if (a == "--denoise") denoise = (uint32_t)std::atoi(next());
         else if (a == "--scale") scale = std::atof(next());
+        else if (a == "--tonemap") tonemap = (uint32_t)std::atoi(next());
+        else if (a == "--auto-exposure") auto_exposure = true;
         else if (a == "--hud") hud = true;
         else if (a == "--out") out = next();
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -100,6 +105,10 @@ int main(int argc, char** argv)
             for (const auto& kv : {std::pair<const char*, double>{"denoise", (double)denoise}, {"denoise_temporal", 16.0}, {"denoise_motion", 1.0}})
                 if (rfw_hip_set_option(renderer->raw(), kv.first, kv.second) != RFW_HIP_OK) throw std::runtime_error(rfw_hip_last_error(renderer->raw()));
 
+        if (tonemap)
+            for (const auto& kv : {std::pair<const char*, double>{"tonemap", (double)tonemap}, {"auto_exposure", auto_exposure ? 1.0 : 0.0}})
+                if (rfw_hip_set_option(renderer->raw(), kv.first, kv.second) != RFW_HIP_OK) throw std::runtime_error(rfw_hip_last_error(renderer->raw()));
+
         const uint64_t px = (uint64_t)width * height;
         std::vector<uint32_t*> ring(8, nullptr); // presented frames land here, 8 frames of slack
         for (uint32_t*& p : ring)
@@ -143,6 +152,13 @@ int main(int argc, char** argv)
         std::printf("%u frames of %ux%u, %llu triangles, %u animated instances: %.2f ms per frame (%.0f frames/s), ~%.0f Mrays/s, every frame presented to host memory\n",
                     frames, width, height, (unsigned long long)scene.triangle_count(), nx * nz, secs / frames * 1e3, frames / secs,
                     (double)rays * frames / secs / 1e6);
+
+        if (tonemap) { // what the display transform applied to the last frame
+            float state[4] = {};
+            uint64_t got = 0;
+            if (rfw_hip_debug_read(renderer->raw(), "display_state", state, sizeof(state), &got) != RFW_HIP_OK) throw std::runtime_error(rfw_hip_last_error(renderer->raw()));
+            if (got == sizeof(state)) std::printf("tonemap %u, %s exposure: the last frame was shown with exposure %.6g\n", tonemap, auto_exposure ? "automatic" : "manual", state[0]);
+        }
 
         const uint32_t* last = ring[(frames - 1) % ring.size()];
         if (FILE* fp = std::fopen(out.c_str(), "wb")) {
