@@ -134,7 +134,7 @@ typedef struct {
      * records the boundary hands over are not counted */
     uint64_t accel_bytes;
     uint32_t packet_copies;
-    uint32_t pad;
+    uint32_t single_space;   /* 1: frames are traced through the single-space kernels (every instance the identity, one per mesh; option "single_space"); takes the place of the former padding word: the struct's size is unchanged */
 } rfw_hip_scene_stats;
 
 /* Hit record of the ray-query extension: what ray_gen/ray_extend store per path
@@ -347,6 +347,7 @@ RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
  *                  "spatial_splits" (threshold; 0 = off), "packet_trace" (bit 0 camera rays, bit 1 / 2 shadow rays as wavefront packets),
  *                  "shade_group" 0 | 256 | 512, "tlas_fused" 0 | 1 | 2 (the TLAS of <= 16 384 instances by one workgroup + one finishing launch:
  *                  never | always | where the instance has frame slots (default) — csrc/lbvh.hip, k_tlas_fused)
+ *                  "single_space" 0 | 1 (default 1: a scene of identity instances, one per mesh, is traced as one tree in one space; the image is the same)
  *   multi-GPU      "gather_format" 0 | 1 | 2, "present_rank" r (see rfw_hip_shard_info), "p2p_timeout_ms" (see rfw_hip_p2p_*) */
 RFW_HIP_API int rfw_hip_set_option(void* instance, const char* key, double value);
 /* tonemapped frame, RGBA32F, sqrt(acc/samples) (backends/gpu-rt/shaders/blit.comp:15-23); n_floats = w*h*4 of the WINDOW size */

@@ -104,13 +104,14 @@ SceneDev scene_dev(Instance* I)
     s.instances = TL->d_xforms.ptr;
     s.instance_normals = TL->d_normals.ptr;
     s.meshes = S->d_mesh_records.ptr;
-    s.blas_nodes = S->d_blas_nodes.ptr;
     s.tlas_wide = TL->d_tlas_wide.ptr;
     s.blas_wide = S->d_blas_wide.ptr;
     s.tlas_wide_stride = (uint32_t)(TL->d_tlas_oct.cap / kPacketNodeCopies); // (both forms of the copies share the stride; the packet form may be absent)
     s.blas_wide_stride = (uint32_t)(S->d_blas_oct.cap / kPacketNodeCopies);
     s.tlas_oct = TL->d_tlas_oct.ptr;
     s.blas_oct = S->d_blas_oct.ptr;
+    s.blas_oct_abs = S->d_blas_oct_abs.ptr;
+    s.ss_root = (S->single_space_opt != 0 && TL->ss_ready && S->d_blas_oct_abs.ptr) ? TL->ss_root : 0u; // (TL's TLAS and graft are of one instances_version; a graft's root is never node 0)
     s.tri_packets = S->d_packets.ptr;
     s.triangles = S->d_triangles.ptr;
     const Instance::Tables& tb = S->tables[S->tables_version % Instance::kTableVersions];
@@ -728,7 +729,7 @@ void rfw_hip_destroy(void* inst)
         if (I->scene_ready) (void)hipEventDestroy(I->scene_ready);
         if (I->frame_done) (void)hipEventDestroy(I->frame_done);
         if (I->download_done) (void)hipEventDestroy(I->download_done);
-        I->d_blas_nodes.release(); I->d_tlas_nodes.release(); I->d_blas_wide.release(); I->d_tlas_wide.release(); I->d_blas_oct.release(); I->d_tlas_oct.release(); I->d_blas_raw.release(); I->d_tlas_raw.release(); I->d_packets.release(); I->d_triangles.release();
+        I->d_blas_nodes.release(); I->d_tlas_nodes.release(); I->d_blas_wide.release(); I->d_tlas_wide.release(); I->d_blas_oct.release(); I->d_blas_oct_abs.release(); I->d_tlas_oct.release(); I->d_blas_raw.release(); I->d_tlas_raw.release(); I->d_packets.release(); I->d_triangles.release();
         I->d_mesh_records.release(); I->d_matrices.release(); I->d_mesh_of_instance.release(); I->d_tlas_prims.release();
         I->d_xforms.release(); I->d_normals.release();
         for (auto& tb : I->tables) { tb.materials.release(); tb.area.release(); tb.point.release(); tb.spot.release(); tb.dir.release(); }
@@ -938,6 +939,13 @@ int rfw_hip_set_option(void* inst, const char* key, double value)
             for (auto& kv : I->meshes) kv.second.dirty = true;
             I->meshes_dirty = true;
             I->layout_valid = false;
+        }
+    }
+    else if (k == "single_space") { // 1: scenes of identity instances, one per mesh, are traced as one tree in one space; 0: never
+        const int v = value != 0.0 ? 1 : 0;
+        if (v != I->single_space_opt) {
+            I->single_space_opt = v; // off: from the next frame; on: the next synchronize() qualifies the scene and prepares it
+            if (v) I->instances_dirty = true;
         }
     }
     else if (k == "shade_group") { // threads per k_shade workgroup: 0 = automatic (do_render), 256, 512

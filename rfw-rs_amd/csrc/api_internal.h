@@ -313,6 +313,18 @@ struct Instance {
     // [oct * stride + i] with stride = the capacity of the quantised array; nullptr when the copies would not fit kMaxPacketNodeBytes
     DevBuf<PacketNode> d_blas_wide, d_tlas_wide;
     DevBuf<Node4Q> d_blas_oct, d_tlas_oct; // the same copies as the one-ray-per-lane kernels read them (make_octant_node), same stride
+    // Single-space scenes (DESIGN.md "Single-space scenes"; option "single_space": 1 = where the scene qualifies, 0 = never).  Owner: the copies
+    // of d_blas_oct with absolute child references (same stride; allocated when a scene first qualifies), whether the scene qualified at the last
+    // synchronize(), the instance id written into each mesh's packets, and which BLAS build the copies were made from.  Per TLAS holder
+    // (tlas_of): whether its latest TLAS has a graft, and the graft's root.
+    DevBuf<Node4Q> d_blas_oct_abs;
+    int single_space_opt = 1;
+    bool ss_candidate = false;
+    std::map<uint32_t, uint32_t> ss_gid_of_mesh;
+    uint64_t blas_serial = 0, ss_expanded_serial = ~0ull;
+    uint32_t blas_slots_used = 0; // node slots of d_blas_nodes that mesh regions occupy (the grafts lie at the far end of the arrays)
+    bool ss_ready = false;
+    uint32_t ss_root = 0;
     DevBuf<TriPacket> d_packets;
     DevBuf<rfw_rt_triangle> d_triangles;
     DevBuf<MeshRecord> d_mesh_records;
@@ -595,6 +607,11 @@ inline bool render_size_of(const uint32_t w, const uint32_t h, const double scal
     do {                                                                                                                                            \
         if (scaled(inst)) return fail(inst, RFW_HIP_E_STATE, what ": not available where the render size differs from the window size (a scaled frame is not exchanged)"); \
     } while (0)
+// Single-space scenes: at most this many instances qualify (C4 as 65 meshes with room to spare); a graft — the TLAS's nodes and a chain node
+// or more per leaf of several instances — then takes at most twice as many node slots, reserved per TLAS holder at the far end of the mesh node arrays
+constexpr uint32_t kSingleSpaceMaxInstances = 256;
+constexpr uint32_t kGraftSlots = 2 * kSingleSpaceMaxInstances;
+inline uint32_t graft_reserve(const Instance* I) { return (uint32_t)(1 + I->slots.size()) * kGraftSlots; }
 inline Instance* scene_of(Instance* I) { return I->scene ? I->scene : I; }
 inline const Instance* scene_of(const Instance* I) { return I->scene ? I->scene : I; }
 void p2p_release(Instance* I);

@@ -330,6 +330,13 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
         if (written) *written = n;
         return RFW_HIP_OK;
     }
+    if (w == "single_space") { // (the graft's root in the mesh node arrays — 0: the latest TLAS has none —, the arrays' stride, the graft's node slots)
+        const uint32_t v[3] = {I->ss_ready ? I->ss_root : 0u, (uint32_t)(I->d_blas_oct.cap / kPacketNodeCopies), kGraftSlots};
+        const uint64_t n = std::min<uint64_t>(bytes, sizeof(v));
+        std::memcpy(dst, v, n);
+        if (written) *written = n;
+        return RFW_HIP_OK;
+    }
     if (w == "ov_stats") { // the 2D layer of the latest frame: primitives drawn, primitives dropped, bin words written
         HIP_TRY(I, hipStreamSynchronize(I->stream));
         const uint32_t np = (uint32_t)std::min<size_t>(I->ov_frame_prims, I->d_ov_tap.cap);
@@ -368,6 +375,11 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
     else if (w == "xforms") { src = I->d_xforms.ptr; avail = I->n_instances * sizeof(InstanceXform); }
     else if (w == "normals") { src = I->d_normals.ptr; avail = I->n_instances * sizeof(InstanceNormal); }
     else if (w == "blas_raw") { src = I->d_blas_raw.ptr; avail = (uint64_t)I->d_blas_raw.cap * sizeof(Node4); }       // device builders: f32 nodes before quantisation
+    else if (w == "blas_graft") { // single-space scenes: octant copy 0 of the node slots of this instance's own graft (debug_read "single_space" says where they lie)
+        const size_t stride = I->d_blas_oct.cap / kPacketNodeCopies;
+        if (I->ss_ready && I->d_blas_oct_abs.ptr && I->ss_root + (size_t)kGraftSlots <= stride) { src = I->d_blas_oct_abs.ptr + I->ss_root; avail = (uint64_t)kGraftSlots * sizeof(Node4Q); }
+    }
+    else if (w == "blas_oct_abs") { src = I->d_blas_oct_abs.ptr; avail = (uint64_t)std::min<size_t>(I->blas_slots_used, I->d_blas_oct_abs.cap) * sizeof(Node4Q); } // octant copy 0 of the mesh regions, absolute references
     else if (w == "blas_order") { src = I->d_blas_order.ptr; avail = (uint64_t)I->d_blas_order.cap * 4; }           // leaf-ordered primitive ids per mesh
     else if (w == "triangles") { src = I->d_triangles.ptr; avail = I->n_tris * sizeof(rfw_rt_triangle); } // static meshes, then the skinned copies
     else return fail(I, RFW_HIP_E_INVALID, "debug_read: unknown buffer " + w);

@@ -7,6 +7,8 @@
 
 using namespace rfwapi;
 
+static_assert(sizeof(rfw_hip_scene_stats) == 96 && offsetof(rfw_hip_scene_stats, single_space) == 92, "rfw_hip_scene_stats is a public POD (rfw-rs_amd/pod.py mirrors it): new fields need a new RFW_HIP_ABI_VERSION");
+
 namespace rfwapi {
 // The per-octant node copies follow the quantised arrays: eight copies, stride = the quantised array's capacity, in two forms — Node4Q for
 // the one-ray-per-lane kernels (always) and PacketNode for the packet kernels (`want_wide`: 1 KB per node slot, so only where a packet kernel
@@ -443,7 +445,8 @@ int layout_records(Instance* I, FullLayout& L)
     assign_logical_ids(I);
     HIP_TRY(I, I->d_triangles.ensure(L.tri_total));
     HIP_TRY(I, I->d_packets.ensure(L.tri_total));
-    HIP_TRY(I, I->d_blas_nodes.ensure(L.node_total));
+    HIP_TRY(I, I->d_blas_nodes.ensure((size_t)L.node_total + graft_reserve(I))); // (+ room for the grafts of single-space scenes at the far end)
+    I->blas_slots_used = L.node_total;
     HIP_TRY(I, follow_copies(I->d_blas_wide, I->d_blas_oct, I->d_blas_nodes, 0, I->stream, blas_wide_wanted(I, L.tri_total)));
     HIP_TRY(I, I->d_blas_raw.ensure(L.node_total));
     HIP_TRY(I, I->d_blas_order.ensure(L.tri_total));
@@ -637,7 +640,8 @@ int build_blas_device_incremental(Instance* I)
     HIP_TRY(I, I->d_blas_order.grow_keep(I->tri_end, I->d_blas_order.cap, I->stream));
     {
         const size_t nodes_before = I->d_blas_nodes.cap; // (the regions in use end below the old capacity)
-        HIP_TRY(I, I->d_blas_nodes.grow_keep(I->node_end, I->d_blas_nodes.cap, I->stream));
+        HIP_TRY(I, I->d_blas_nodes.grow_keep((size_t)I->node_end + graft_reserve(I), I->d_blas_nodes.cap, I->stream));
+        I->blas_slots_used = I->node_end;
         HIP_TRY(I, follow_copies(I->d_blas_wide, I->d_blas_oct, I->d_blas_nodes, nodes_before, I->stream, blas_wide_wanted(I, I->tri_end)));
     }
     HIP_TRY(I, I->d_blas_raw.grow_keep(I->node_end, 0, I->stream)); // build output only: nothing to keep
@@ -750,7 +754,8 @@ int build_blas_host(Instance* I)
     assign_logical_ids(I);
     I->n_tris = tri_total;
     I->n_blas_nodes = node_total;
-    HIP_TRY(I, I->d_blas_nodes.ensure(node_total)); // room for the skinned copies behind the static meshes
+    HIP_TRY(I, I->d_blas_nodes.ensure((size_t)node_total + graft_reserve(I))); // room for the skinned copies behind the static meshes (+ the grafts of single-space scenes)
+    I->blas_slots_used = node_total;
     HIP_TRY(I, follow_copies(I->d_blas_wide, I->d_blas_oct, I->d_blas_nodes, 0, I->stream, blas_wide_wanted(I, tri_total)));
     HIP_TRY(I, I->d_packets.ensure(tri_total));
     HIP_TRY(I, I->d_triangles.ensure(tri_total));
@@ -763,6 +768,82 @@ int build_blas_host(Instance* I)
     if ((rc = upload(I, I->d_mesh_records, I->mesh_records.data(), I->mesh_records.size()))) return rc;
     HIP_TRY(I, hipStreamSynchronize(I->stream)); // the host vectors above go out of scope
     return RFW_HIP_OK;
+}
+
+// ---- Single-space scenes (DESIGN.md "Single-space scenes")
+// Does the scene qualify, by what the host holds?  Every live instance (a mesh with triangles, a matrix that is not the zero matrix) has the
+// identity matrix bit for bit (1.0f and +0.0f), no mesh has two of them, there are 1 ... kSingleSpaceMaxInstances of them, no skinned copies,
+// the TLAS is built on the device (the graft is made from its tree), and absolute leaf references fit their 27 bits.  gid_of_mesh: the id of
+// each mesh's one instance, numbered as build_instances numbers them.
+bool single_space_candidate(const Instance* I, std::map<uint32_t, uint32_t>& gid_of_mesh)
+{
+    gid_of_mesh.clear();
+    if (I->single_space_opt == 0 || !I->tlas_on_device || !wanted_derived(I).empty()) return false;
+    static const rfw_mat4 identity = {{1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f}};
+    uint32_t gid = 0;
+    uint64_t tris = 0;
+    for (const auto& kv : I->inst_lists) {
+        const auto mit = I->meshes.find(kv.first);
+        const bool mesh_ok = mit != I->meshes.end() && mit->second.n_refs > 0;
+        for (size_t k = 0; k < kv.second.matrices.size(); k++, gid++) {
+            if (!mesh_ok || is_zero_matrix(kv.second.matrices[k])) continue;
+            if (std::memcmp(&kv.second.matrices[k], &identity, sizeof(rfw_mat4)) != 0) return false; // (bitwise: -0.0f is not +0.0f)
+            if (!gid_of_mesh.emplace(kv.first, gid).second) return false;
+            tris += mit->second.n_refs;
+        }
+    }
+    return !gid_of_mesh.empty() && gid_of_mesh.size() <= kSingleSpaceMaxInstances && tris <= kLeafFirstMask;
+}
+// What a qualifying scene needs besides its grafts, on the owner's stream (the caller has ordered it behind the frames in flight): the octant
+// copies of the mesh nodes with absolute child references (d_blas_oct_abs, and PacketNode::pad of the packet form), made from the quantised
+// nodes, and each mesh's instance id in its packets.
+// ... and by what the BLAS build laid out: every instanced mesh's regions lie inside the node copies and below the 27 bits of an absolute leaf
+// reference (meshes without instances may lie in front of them in the buffers), and the grafts have room behind the regions in use.  A scene
+// that fails this does not qualify: it keeps the two-level path.
+bool single_space_layout_fits(const Instance* I, const std::map<uint32_t, uint32_t>& gid_of_mesh)
+{
+    const uint64_t stride = I->d_blas_oct.cap / kPacketNodeCopies;
+    if ((uint64_t)I->blas_slots_used + graft_reserve(I) > stride) return false;
+    for (const auto& kv : gid_of_mesh) {
+        const auto it = I->mesh_index.find(kv.first);
+        if (it == I->mesh_index.end()) return false;
+        const MeshRecord& r = I->mesh_records[it->second];
+        if ((uint64_t)r.node_base + r.node_count > I->blas_slots_used || (uint64_t)r.tri_base + r.tri_count > kLeafFirstMask) return false;
+    }
+    return true;
+}
+int prepare_single_space(Instance* I, const std::map<uint32_t, uint32_t>& gid_of_mesh)
+{
+    if (I->d_blas_oct_abs.cap != I->d_blas_oct.cap) {
+        I->d_blas_oct_abs.release();
+        HIP_TRY(I, I->d_blas_oct_abs.ensure(I->d_blas_oct.cap));
+        if (I->d_blas_oct_abs.cap != I->d_blas_oct.cap) { I->d_blas_oct_abs.release(); return fail(I, RFW_HIP_E_STATE, "single space: node copies of an unexpected size"); }
+    }
+    const uint32_t stride = (uint32_t)(I->d_blas_oct.cap / kPacketNodeCopies);
+    for (const auto& kv : gid_of_mesh) { // mesh by mesh (only instanced meshes can be reached; after incremental builds the records are in no particular order)
+        const uint32_t q = I->mesh_index.at(kv.first);
+        const MeshRecord& r = I->mesh_records[q];
+        launch_ss_expand(I->stream, I->d_blas_nodes.ptr, I->d_blas_oct_abs.ptr, I->d_blas_wide.ptr, stride, r.node_count, I->blas_on_device ? I->d_mesh_node_counts.ptr + q : nullptr,
+                         r.node_base, r.tri_base);
+        launch_ss_packet_ids(I->stream, I->d_packets.ptr + r.tri_base, r.tri_count, kv.second);
+    }
+    HIP_TRY(I, hipGetLastError());
+    I->ss_gid_of_mesh = gid_of_mesh;
+    I->ss_expanded_serial = I->blas_serial;
+    return RFW_HIP_OK;
+}
+// Behind the device TLAS build of holder T: where the scene qualifies, T's graft — its TLAS tree over the meshes' root nodes — in T's own
+// kGraftSlots node slots at the far end of the absolute copies (so that every frame slot keeps the graft its frames read)
+void graft_tlas(Instance* I, Instance* T, uint32_t n_valid)
+{
+    const uint32_t stride = (uint32_t)(I->d_blas_oct.cap / kPacketNodeCopies);
+    if (!I->ss_candidate || n_valid == 0 || n_valid > kSingleSpaceMaxInstances || !I->d_blas_oct_abs.ptr || I->d_blas_oct_abs.cap != I->d_blas_oct.cap ||
+        T->slot_index > I->slots.size() || (uint64_t)I->blas_slots_used + graft_reserve(I) > stride)
+        return;
+    const uint32_t root = stride - (T->slot_index + 1u) * kGraftSlots;
+    launch_ss_graft(T->stream, T->d_tlas_raw.ptr, n_valid, T->d_node_count.ptr, T->d_tlas_prims.ptr, T->d_xforms.ptr, root, I->d_blas_oct_abs.ptr, I->d_blas_wide.ptr, stride);
+    T->ss_root = root;
+    T->ss_ready = true;
 }
 
 // instances + TLAS (gpu-rt/src/lib.rs:1576-1615): global instance id = mesh_base[mesh] + slot
@@ -822,6 +903,7 @@ int build_instances(Instance* I, Instance* T)
     }
     T->n_instances = n_all;
     T->n_valid_instances = n_valid;
+    T->ss_ready = false; // (graft_tlas, behind the device TLAS build of a scene that qualifies)
     HIP_TRY(I, T->d_matrices.ensure(n_all));
     HIP_TRY(I, T->d_mesh_of_instance.ensure(n_all));
     HIP_TRY(I, T->d_valid_gids.ensure(n_all));
@@ -854,6 +936,8 @@ int build_instances(Instance* I, Instance* T)
                            I->d_mesh_records.ptr, (uint32_t)n_all, T->d_xforms.ptr, T->d_normals.ptr);
         HIP_TRY(I, hipGetLastError());
         T->n_tlas_nodes = 0; // read back lazily (get_scene_stats)
+        graft_tlas(I, T, n_valid);
+        HIP_TRY(I, hipGetLastError());
         HIP_TRY(I, hipEventRecord(T->stage_event[T->stage_next], s));
         T->stage_pending[T->stage_next] = true;
         T->stage_next = (T->stage_next + 1) % Instance::kStages;
@@ -930,6 +1014,7 @@ int build_instances(Instance* I, Instance* T)
                               T->d_node_count.ptr));
         launch_quantize_nodes(s, T->d_tlas_raw.ptr, T->d_tlas_nodes.ptr, copies_of(T->d_tlas_wide, T->d_tlas_oct), 0u, std::max<uint32_t>(n_valid, 1u), T->d_node_count.ptr);
         launch_gather_u32(s, T->d_valid_gids.ptr, T->d_tlas_order.ptr, n_valid, T->d_tlas_prims.ptr);
+        graft_tlas(I, T, n_valid);
         HIP_TRY(I, hipGetLastError());
         T->n_tlas_nodes = 0; // read back lazily (get_scene_stats)
         HIP_TRY(I, hipEventRecord(T->stage_event[T->stage_next], s));
@@ -1142,7 +1227,13 @@ int do_synchronize(Instance* I)
     // does this call queue work on the owner's stream that the frame slots have to wait for (anything but a per-slot TLAS update)?
     // (per_slot_tlas() may flip inside build_blas_* when skinned copies appear or disappear; meshes_dirty covers both directions)
     // (material and light edits do not count: they go into a new version of their tables, see upload_tables)
-    const bool shared_work = I->meshes_dirty || I->textures_dirty || (I->instances_dirty && !per_slot_tlas(I));
+    // single-space scenes: qualified again whenever meshes or instances changed; what a qualifying scene needs written into the shared mesh
+    // buffers (absolute node copies after a BLAS build, instance ids in the packets when they changed) is work on the owner's stream too
+    std::map<uint32_t, uint32_t> ss_gids;
+    const bool ss_eval = I->meshes_dirty || I->instances_dirty;
+    const bool ss_qualifies = ss_eval ? single_space_candidate(I, ss_gids) : I->ss_candidate;
+    const bool ss_write = ss_eval && ss_qualifies && (I->meshes_dirty || ss_gids != I->ss_gid_of_mesh || I->ss_expanded_serial != I->blas_serial);
+    const bool shared_work = I->meshes_dirty || I->textures_dirty || (I->instances_dirty && !per_slot_tlas(I)) || ss_write;
     if (!I->slots.empty() && shared_work) {
         // frames still in flight on the slots read the scene that is about to change: the uploads queue behind them
         for (Instance* c : I->slots)
@@ -1155,7 +1246,12 @@ int do_synchronize(Instance* I)
         I->ms_blas_build = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         I->meshes_dirty = false;
         I->instances_dirty = true;
+        I->blas_serial++;
         any_change = true;
+    }
+    if (ss_eval) {
+        I->ss_candidate = ss_qualifies && I->derived.empty() && single_space_layout_fits(I, ss_gids);
+        if (I->ss_candidate && ss_write && (rc = prepare_single_space(I, ss_gids))) return rc;
     }
     if (I->instances_dirty) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -1932,10 +2028,10 @@ int rfw_hip_get_scene_stats(void* inst, rfw_hip_scene_stats* out)
     }
     out->triangles = I->n_tris_logical; // the caller's triangles (I->n_tris also counts the duplicates of split triangles)
     out->split_references = I->n_split_refs;
-    out->accel_bytes = I->d_blas_nodes.cap * sizeof(Node4Q) + I->d_blas_oct.cap * sizeof(Node4Q) + I->d_blas_wide.cap * sizeof(PacketNode) + I->d_packets.cap * sizeof(TriPacket) +
+    out->accel_bytes = I->d_blas_nodes.cap * sizeof(Node4Q) + I->d_blas_oct.cap * sizeof(Node4Q) + I->d_blas_oct_abs.cap * sizeof(Node4Q) + I->d_blas_wide.cap * sizeof(PacketNode) + I->d_packets.cap * sizeof(TriPacket) +
                        I->d_tlas_nodes.cap * sizeof(Node4Q) + I->d_tlas_oct.cap * sizeof(Node4Q) + I->d_tlas_wide.cap * sizeof(PacketNode);
     out->packet_copies = I->d_blas_wide.ptr ? 1u : 0u;
-    out->pad = 0u;
+    out->single_space = (I->single_space_opt != 0 && tlas_of(I)->ss_ready && I->d_blas_oct_abs.ptr) ? 1u : 0u;
     out->instances = I->n_valid_instances;
     out->blas_nodes = I->n_blas_nodes;
     if (I->tlas_on_device && I->d_node_count.ptr && I->synchronized) {

@@ -13,7 +13,11 @@ struct SceneDev {
     const InstanceXform* instances;
     const InstanceNormal* instance_normals;
     const MeshRecord* meshes;         // per mesh record: where it lives, and the triangle-id offset the boundary reports
-    const Node4Q* blas_nodes;
+    // Single-space scenes (DESIGN.md "Single-space scenes"): the copies of blas_oct with ABSOLUTE child references (PacketNode::pad of blas_wide
+    // holds the same references), or nullptr.  The trace launches take their single-space twins when ss_root != 0: the root of this frame's
+    // graft in those arrays.  (Both sit where the struct had an unread pointer — the quantised mesh nodes, which no kernel reads — and four
+    // bytes of padding: the kernels' argument block is laid out as it was.)
+    const Node4Q* blas_oct_abs;
     // the same trees as the packet kernels read them (traverse_packet.h: a node is fetched once per wavefront through the scalar cache):
     // eight copies, one per ray octant, child boxes as floats, near / far planes picked and children sorted for the octant (PacketNode);
     // nullptr = not available
@@ -34,6 +38,7 @@ struct SceneDev {
     const TexDesc* tex_desc;
     uint32_t n_textures;
     TexDesc skybox;             // mips == 0: no skybox image, a miss adds the constant sky colour
+    uint32_t ss_root;           // != 0: a single-space frame (see blas_oct_abs)
     const uint8_t* blue_noise;  // kBlueNoiseWords table entries (each a byte), or nullptr: every sample draws from xorshift
     uint32_t* spill;
     uint32_t spill_stride;
@@ -89,6 +94,15 @@ void launch_tlas_finish(hipStream_t s, const Node4* raw, Node4Q* out, const Octa
 void launch_expand_nodes(hipStream_t s, const Node4Q* in, const OctantCopies& oc, uint32_t first, uint32_t n, const uint32_t* live = nullptr); // the copies of already quantised nodes
 // the same for slots [0, n) holding SEVERAL trees: record k's tree lives at recs[k].node_base and has counts[k] nodes (both on the device)
 void launch_quantize_regions(hipStream_t s, const Node4* in, Node4Q* out, const OctantCopies& oc, uint32_t n, const MeshRecord* recs, const uint32_t* counts, uint32_t n_recs);
+// Single-space scenes: expand — the octant copies of ONE mesh's quantised nodes (slots node_base .. node_base + n of the arrays) with
+// absolute child references into abs_oct, the references also into PacketNode::pad of `wide` (nullable); live (nullable): the tree's node
+// count on the device, else all n slots hold nodes.  graft —
+// the TLAS tree `raw` (its first *live of n_nodes_max nodes) as nodes root .. of both arrays, its leaves replaced by the meshes' root nodes
+// (room for n_nodes_max + the instance list's length).  packet_ids — TriPacket::pad of one mesh's packets = the id of its one instance.
+void launch_ss_expand(hipStream_t s, const Node4Q* in, Node4Q* abs_oct, PacketNode* wide, uint32_t stride, uint32_t n, const uint32_t* live, uint32_t node_base, uint32_t tri_base);
+void launch_ss_graft(hipStream_t s, const Node4* raw, uint32_t n_nodes_max, const uint32_t* live, const uint32_t* prims, const InstanceXform* xf, uint32_t root, Node4Q* abs_oct,
+                     PacketNode* wide, uint32_t stride);
+void launch_ss_packet_ids(hipStream_t s, TriPacket* packets, uint32_t n, uint32_t gid);
 // linear: render modes 1-6 finalise as acc / samples instead of sqrt(acc / samples) (the accumulator read is the same either way)
 void launch_assemble(hipStream_t s, const CameraParams& cam, const void* gathered, bool rgb, bool accumulator, uint64_t slab_elems, float4* frame,
                      uint32_t samples, bool linear = false);

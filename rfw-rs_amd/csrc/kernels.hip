@@ -78,7 +78,6 @@ RFW_DI SceneView scene_view(const SceneDev& sc)
     v.tlas_nodes = sc.tlas_nodes;
     v.tlas_prims = sc.tlas_prims;
     v.instances = sc.instances;
-    v.blas_nodes = sc.blas_nodes;
     v.tlas_oct = sc.tlas_oct;
     v.blas_oct = sc.blas_oct;
     v.tlas_oct_stride = sc.tlas_wide_stride;
@@ -89,7 +88,21 @@ RFW_DI SceneView scene_view(const SceneDev& sc)
     v.spill_rows = sc.spill_rows;
     v.overflow_flag = sc.overflow_flag;
     v.counters = sc.counters;
+    v.ss_root = 0u;
     return v;
+}
+// the view of the single-space flavours (traverse.h, SS): the mesh trees with absolute child references, entered at the frame's graft
+RFW_DI SceneView scene_view_ss(const SceneDev& sc)
+{
+    SceneView v = scene_view(sc);
+    v.blas_oct = sc.blas_oct_abs;
+    v.ss_root = sc.ss_root;
+    return v;
+}
+template <bool SS> RFW_DI SceneView scene_view_of(const SceneDev& sc)
+{
+    if constexpr (SS) return scene_view_ss(sc);
+    else return scene_view(sc);
 }
 
 // the first workgroup of a frame's first kernel clears the counter block the NEXT frame of this stream will use (SceneDev::counters_next)
@@ -323,11 +336,11 @@ RFW_DI void mark_no_path(const PathDev& p, const uint32_t idx, const CameraSlot&
 }
 // One ray per lane: only the lanes that hold a pixel trace.  (What such a lane does stays in ONE branch: with the set-up, the trace and the hit
 // store under a condition each, the compiler keeps three regions: k_primary<false> 812 -> 816 vector, 441 -> 447 scalar instructions.)
-template <bool COUNT, bool BATCH>
+template <bool COUNT, bool BATCH, bool SS = false>
 RFW_DI void primary_per_lane(const CameraParams& cam, const BatchViews* views, const SceneDev& sc, const PathDev& p)
 {
     clear_next_counters(sc);
-    __shared__ uint32_t s_stack[kTraceLdsRows * kTraceBlock];
+    __shared__ uint32_t s_stack[(SS ? kStackLds : kTraceLdsRows) * kTraceBlock]; // (SS: no parked ray above the stack)
     const uint32_t block = xcd_block(blockIdx.x);
     const uint32_t idx = block * kTraceBlock + threadIdx.x;
     TravCounters tc{0, 0, 0};
@@ -337,14 +350,14 @@ RFW_DI void primary_per_lane(const CameraParams& cam, const BatchViews* views, c
         begin_camera_path<BATCH>(cam, views, sc, p, idx, cs, O, D);
         float t = 1e26f, hu = 0.0f, hv = 0.0f;
         int32_t hi = -1, ht = -1;
-        traverse<false, COUNT>(scene_view(sc), O, D, 1e-4f, t, hu, hv, hi, ht, s_stack, threadIdx.x, block * kTraceBlock, tc);
+        traverse<false, COUNT, false, SS>(scene_view_of<SS>(sc), O, D, 1e-4f, t, hu, hv, hi, ht, s_stack, threadIdx.x, block * kTraceBlock, tc);
         p.hit[0][idx] = pack_hit(hi, ht, t, hu, hv);
     } else mark_no_path(p, idx, cs);
     flush_counters<COUNT>(sc.counters, tc, 0);
 }
 // The packet flavour (traverse_packet.h): the 64 camera rays of an 8x8-pixel block walk the tree together on one shared stack, the lanes without a
 // pixel idle among them.  Same rays, same triangle tests, same image; no LDS.
-template <bool COUNT, bool BATCH>
+template <bool COUNT, bool BATCH, bool SS = false>
 RFW_DI void primary_packet(const CameraParams& cam, const BatchViews* views, const SceneDev& sc, const PathDev& p)
 {
     clear_next_counters(sc);
@@ -357,8 +370,8 @@ RFW_DI void primary_packet(const CameraParams& cam, const BatchViews* views, con
     float t = 1e26f, hu = 0.0f, hv = 0.0f;
     int32_t hi = -1, ht = -1;
     bool occluded;
-    const SceneView sv = scene_view(sc);
-    traverse_packet<false, COUNT>(sv, sc.tlas_wide, sc.tlas_wide_stride, sc.blas_wide, sc.blas_wide_stride, cs.valid, O, D, 1e-4f, t, hu, hv, hi, ht, occluded, tc);
+    const SceneView sv = scene_view_of<SS>(sc);
+    traverse_packet<false, COUNT, false, SS>(sv, sc.tlas_wide, sc.tlas_wide_stride, sc.blas_wide, sc.blas_wide_stride, cs.valid, O, D, 1e-4f, t, hu, hv, hi, ht, occluded, tc);
     if (cs.valid) p.hit[0][idx] = pack_hit(hi, ht, t, hu, hv);
     else mark_no_path(p, idx, cs);
     flush_counters<COUNT>(sc.counters, tc, 0);
@@ -371,6 +384,26 @@ template <bool COUNT> __global__ __launch_bounds__(kTraceBlock, kTraceWaves) voi
 template <bool COUNT> __global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_primary_packet(const CameraParams cam, const SceneDev sc, const PathDev p)
 {
     primary_packet<COUNT, false>(cam, nullptr, sc, p);
+}
+// The single-space twins (traverse.h, SS; DESIGN.md "Single-space scenes"), launched where the frame's scene qualifies.  Kernels of their own, not a
+// parameter of the ones above: those keep their names and their code, instruction for instruction (tests/test_render_modes_on_cpu.py pins both).
+template <bool COUNT> __global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_primary_ss(const CameraParams cam, const SceneDev sc, const PathDev p)
+{
+    primary_per_lane<COUNT, false, true>(cam, nullptr, sc, p);
+}
+template <bool COUNT> __global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_primary_packet_ss(const CameraParams cam, const SceneDev sc, const PathDev p)
+{
+    primary_packet<COUNT, false, true>(cam, nullptr, sc, p);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_primary_batch_ss(const CameraParams cam, const BatchViews views, const SceneDev sc, const PathDev p)
+{
+    primary_per_lane<COUNT, true, true>(cam, &views, sc, p);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_primary_batch_packet_ss(const CameraParams cam, const BatchViews views, const SceneDev sc, const PathDev p)
+{
+    primary_packet<COUNT, true, true>(cam, &views, sc, p);
 }
 // the same for a batch of independent frames (rfw_hip_render_batch): one launch covers the tiles of every frame of the batch.  A wavefront's 64
 // paths belong to ONE frame, so for the packet flavour they are one 8x8-pixel block of one view as in k_primary_packet
@@ -422,11 +455,10 @@ void launch_extension_keys(hipStream_t s, const SceneDev& sc, const PathDev& p, 
 }
 
 // ---------------------------------------------------------------- ray_extend.comp:245-268
-template <bool COUNT>
-__global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_extend(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce,
-                                                                         const uint32_t* __restrict__ order)
+template <bool COUNT, bool SS>
+RFW_DI void extend_per_lane(const CameraParams& cam, const SceneDev& sc, const PathDev& p, const uint32_t bounce, const uint32_t* __restrict__ order)
 {
-    __shared__ uint32_t s_stack[kTraceLdsRows * kTraceBlock];
+    __shared__ uint32_t s_stack[(SS ? kStackLds : kTraceLdsRows) * kTraceBlock];
     const uint32_t block = xcd_block(blockIdx.x);
     const uint32_t idx = block * kTraceBlock + threadIdx.x;
     const uint32_t count = sc.counters->ext[bounce - 1];
@@ -439,11 +471,23 @@ __global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_extend(const Camer
         const f3 O = mk3(o4.x, o4.y, o4.z), D = mk3(d4.x, d4.y, d4.z);
         float t = 1e26f, hu = 0.0f, hv = 0.0f;
         int32_t hi = -1, ht = -1;
-        const SceneView sv = scene_view(sc);
-        traverse<false, COUNT>(sv, O, D, 1e-4f, t, hu, hv, hi, ht, s_stack, threadIdx.x, block * kTraceBlock, tc);
+        const SceneView sv = scene_view_of<SS>(sc);
+        traverse<false, COUNT, false, SS>(sv, O, D, 1e-4f, t, hu, hv, hi, ht, s_stack, threadIdx.x, block * kTraceBlock, tc);
         p.hit[half][j] = pack_hit(hi, ht, t, hu, hv);
     }
     flush_counters<COUNT>(sc.counters, tc, 1);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_extend(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce,
+                                                                         const uint32_t* __restrict__ order)
+{
+    extend_per_lane<COUNT, false>(cam, sc, p, bounce, order);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_extend_ss(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce,
+                                                                            const uint32_t* __restrict__ order)
+{
+    extend_per_lane<COUNT, true>(cam, sc, p, bounce, order);
 }
 
 // The streaming flavour (traverse.h, traverse_stream): a wavefront owns cam.stream_run x 64 consecutive entries of the extension queue
@@ -469,6 +513,22 @@ struct ExtendStream {
     RFW_DI void advance(const uint64_t idle) { next += (uint32_t)__popcll(idle); }
     RFW_DI void commit(bool, const float t, const float hu, const float hv, const int32_t hi, const int32_t ht) { p.hit[half][j] = pack_hit(hi, ht, t, hu, hv); }
 };
+// The single-space twin's body.  (The two-level kernel below keeps its own: sharing this function moves its instruction count by a few, and
+// tests/test_render_modes_on_cpu.py pins that count exactly; once that pin is re-baselined the two can share one body.)
+template <bool COUNT>
+RFW_DI void extend_streamed(const CameraParams& cam, const SceneDev& sc, const PathDev& p, const uint32_t bounce, const uint32_t* __restrict__ order)
+{
+    __shared__ uint32_t s_stack[kStackLds * kTraceBlock];
+    const uint32_t run = cam.stream_run * kTraceBlock;
+    const uint32_t block = xcd_run(blockIdx.x, 64u / cam.stream_run);
+    const uint32_t count = sc.counters->ext[bounce - 1];
+    if (block * run >= count) return;
+    TravCounters tc{0, 0, 0};
+    ExtendStream st{p, order, bounce & 1u, block * run, min(count, (block + 1u) * run), 0u};
+    const SceneView sv = scene_view_ss(sc);
+    traverse_stream<false, COUNT, false, true>(sv, st, cam.stream_refill & 0xffu, cam.stream_refill >> 8, s_stack, threadIdx.x, blockIdx.x * kTraceBlock, tc);
+    flush_counters<COUNT>(sc.counters, tc, 1);
+}
 template <bool COUNT>
 __global__ __launch_bounds__(kTraceBlock, kStreamWaves) void k_extend_stream(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce,
                                                                                 const uint32_t* __restrict__ order)
@@ -483,6 +543,12 @@ __global__ __launch_bounds__(kTraceBlock, kStreamWaves) void k_extend_stream(con
     const SceneView sv = scene_view(sc);
     traverse_stream<false, COUNT, false>(sv, st, cam.stream_refill & 0xffu, cam.stream_refill >> 8, s_stack, threadIdx.x, blockIdx.x * kTraceBlock, tc);
     flush_counters<COUNT>(sc.counters, tc, 1);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kTraceBlock, kStreamWaves) void k_extend_stream_ss(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce,
+                                                                                   const uint32_t* __restrict__ order)
+{
+    extend_streamed<COUNT>(cam, sc, p, bounce, order);
 }
 
 // ---------------------------------------------------------------- ray_shadow.comp:245-268
@@ -543,10 +609,10 @@ RFW_DI void add_contribution(const PathDev& p, const uint32_t idx)
 
 // (BATCH is not read: a batch needs nothing special here, the queue entry carries the accumulator slot.  Both twins are launched and pinned by
 // tests/test_render_modes_on_cpu.py, so the parameter stays.)
-template <bool COUNT, bool BATCH = false>
-__global__ __launch_bounds__(kTraceBlock, kTraceWavesAny) void k_shadow(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
+template <bool COUNT, bool SS>
+RFW_DI void shadow_per_lane(const CameraParams& cam, const SceneDev& sc, const PathDev& p, const uint32_t bounce)
 {
-    __shared__ uint32_t s_stack[kTraceLdsRowsAny * kTraceBlock];
+    __shared__ uint32_t s_stack[(SS ? kStackLdsAny : kTraceLdsRowsAny) * kTraceBlock];
     const uint32_t launch_block = xcd_block(blockIdx.x);
     const bool far_as_packets = (cam.flags & kFlagPacketShadowFar) != 0u; // (launch_shadow)
     const ShadowBucket b = find_shadow_bucket(sc, bounce, kTraceBlock, launch_block, [&](const uint32_t k) { return far_as_packets && bucket_far_first(cam, k); });
@@ -564,10 +630,10 @@ __global__ __launch_bounds__(kTraceBlock, kTraceWavesAny) void k_shadow(const Ca
         float t, hu, hv;
         load_shadow_ray(p, idx, O, D, t);
         int32_t hi = -1, ht = -1;
-        const SceneView sv = scene_view(sc);
+        const SceneView sv = scene_view_of<SS>(sc);
         const bool far_first = bucket_far_first(cam, bucket);
-        const bool occluded = far_first ? traverse<true, COUNT, true>(sv, O, D, 0.001f, t, hu, hv, hi, ht, s_stack, threadIdx.x, spill_base, tc)
-                                        : traverse<true, COUNT, false>(sv, O, D, 0.001f, t, hu, hv, hi, ht, s_stack, threadIdx.x, spill_base, tc);
+        const bool occluded = far_first ? traverse<true, COUNT, true, SS>(sv, O, D, 0.001f, t, hu, hv, hi, ht, s_stack, threadIdx.x, spill_base, tc)
+                                        : traverse<true, COUNT, false, SS>(sv, O, D, 0.001f, t, hu, hv, hi, ht, s_stack, threadIdx.x, spill_base, tc);
         if (!occluded) {
             // (the entry's index is formed again from the wave-uniform part and the lane: kept across the traversal it is a 64-bit register
             // pair that went to scratch memory at 8 waves per SIMD)
@@ -578,9 +644,40 @@ __global__ __launch_bounds__(kTraceBlock, kTraceWavesAny) void k_shadow(const Ca
     }
     flush_counters<COUNT>(sc.counters, tc, 2);
 }
+template <bool COUNT, bool BATCH = false>
+__global__ __launch_bounds__(kTraceBlock, kTraceWavesAny) void k_shadow(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
+{
+    shadow_per_lane<COUNT, false>(cam, sc, p, bounce);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kTraceBlock, kTraceWavesAny) void k_shadow_ss(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
+{
+    shadow_per_lane<COUNT, true>(cam, sc, p, bounce);
+}
 
 // The packet flavour for the camera paths' shadow rays (bounce 0): the 64 rays of a wavefront start on neighbouring pixels and aim at one
 // light.  One instantiation per visiting order, each launch walking the buckets of its order (as the streaming flavour below).
+// The single-space twin's body.  (The two-level kernel below keeps its own: sharing this function moves its instruction count by a few, and
+// tests/test_render_modes_on_cpu.py pins that count exactly; once that pin is re-baselined the two can share one body.)
+template <bool COUNT, bool FAR>
+RFW_DI void shadow_as_packets(const CameraParams& cam, const SceneDev& sc, const PathDev& p, const uint32_t bounce)
+{
+    const ShadowBucket b = find_shadow_bucket(sc, bounce, kTraceBlock, xcd_block(blockIdx.x), [&](const uint32_t k) { return bucket_far_first(cam, k) != FAR; });
+    if (!b.found) return;
+    const uint32_t local = b.block * kTraceBlock + threadIdx.x;
+    const uint32_t idx = b.bucket * p.capacity + local;
+    TravCounters tc{0, 0, 0};
+    const bool valid = local < b.count;
+    f3 O = mk3(0.0f), D = mk3(0.0f);
+    float t = 1.0f, hu, hv;
+    if (valid) load_shadow_ray(p, idx, O, D, t);
+    int32_t hi = -1, ht = -1;
+    bool occluded;
+    const SceneView sv = scene_view_ss(sc);
+    traverse_packet<true, COUNT, FAR, true>(sv, sc.tlas_wide, sc.tlas_wide_stride, sc.blas_wide, sc.blas_wide_stride, valid, O, D, 0.001f, t, hu, hv, hi, ht, occluded, tc);
+    if (valid && !occluded) add_contribution(p, idx);
+    flush_counters<COUNT>(sc.counters, tc, 2);
+}
 template <bool COUNT, bool FAR>
 __global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_shadow_packet(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
 {
@@ -599,6 +696,11 @@ __global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_shadow_packet(con
     traverse_packet<true, COUNT, FAR>(sv, sc.tlas_wide, sc.tlas_wide_stride, sc.blas_wide, sc.blas_wide_stride, valid, O, D, 0.001f, t, hu, hv, hi, ht, occluded, tc);
     if (valid && !occluded) add_contribution(p, idx);
     flush_counters<COUNT>(sc.counters, tc, 2);
+}
+template <bool COUNT, bool FAR>
+__global__ __launch_bounds__(kTraceBlock, kPacketWaves) void k_shadow_packet_ss(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
+{
+    shadow_as_packets<COUNT, FAR>(cam, sc, p, bounce);
 }
 
 struct ShadowStream {
@@ -624,6 +726,21 @@ struct ShadowStream {
 };
 // One instantiation per visiting order (FAR: hit children by decreasing exit distance): a kernel that holds both traversals spills ~50 scalar
 // registers into vector lanes.  Each launch walks the buckets of its own order only.
+// The single-space twin's body.  (The two-level kernel below keeps its own: sharing this function moves its instruction count by a few, and
+// tests/test_render_modes_on_cpu.py pins that count exactly; once that pin is re-baselined the two can share one body.)
+template <bool COUNT, bool FAR>
+RFW_DI void shadow_streamed(const CameraParams& cam, const SceneDev& sc, const PathDev& p, const uint32_t bounce)
+{
+    __shared__ uint32_t s_stack[kStackLdsAny * kTraceBlock];
+    const uint32_t run = cam.stream_run * kTraceBlock;
+    const ShadowBucket b = find_shadow_bucket(sc, bounce, run, xcd_run(blockIdx.x, 64u / cam.stream_run), [&](const uint32_t k) { return bucket_far_first(cam, k) != FAR; });
+    if (!b.found) return;
+    TravCounters tc{0, 0, 0};
+    ShadowStream st{p, b.bucket * p.capacity, b.block * run, min(b.count, (b.block + 1u) * run), 0u};
+    const SceneView sv = scene_view_ss(sc);
+    traverse_stream<true, COUNT, FAR, true>(sv, st, cam.stream_refill & 0xffu, cam.stream_refill >> 8, s_stack, threadIdx.x, blockIdx.x * kTraceBlock, tc);
+    flush_counters<COUNT>(sc.counters, tc, 2);
+}
 template <bool COUNT, bool FAR>
 __global__ __launch_bounds__(kTraceBlock, kStreamWavesAny) void k_shadow_stream(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
 {
@@ -636,6 +753,11 @@ __global__ __launch_bounds__(kTraceBlock, kStreamWavesAny) void k_shadow_stream(
     const SceneView sv = scene_view(sc);
     traverse_stream<true, COUNT, FAR>(sv, st, cam.stream_refill & 0xffu, cam.stream_refill >> 8, s_stack, threadIdx.x, blockIdx.x * kTraceBlock, tc);
     flush_counters<COUNT>(sc.counters, tc, 2);
+}
+template <bool COUNT, bool FAR>
+__global__ __launch_bounds__(kTraceBlock, kStreamWavesAny) void k_shadow_stream_ss(const CameraParams cam, const SceneDev sc, const PathDev p, const uint32_t bounce)
+{
+    shadow_streamed<COUNT, FAR>(cam, sc, p, bounce);
 }
 
 // ---------------------------------------------------------------- shade.comp:70-266
@@ -1178,6 +1300,80 @@ __global__ __launch_bounds__(256) void k_tlas_finish(const Node4* __restrict__ r
     }
 }
 
+// ---------------------------------------------------------------- single-space scenes (DESIGN.md "Single-space scenes")
+// A child reference of a mesh's tree, relative to the mesh's regions -> absolute: an interior index in the node array, a leaf's first packet in tri_packets
+RFW_DI uint32_t absolute_ref(const uint32_t c, const uint32_t node_base, const uint32_t tri_base)
+{
+    if (c == kInvalidRef) return c;
+    return (c & kLeafBit) ? c + tri_base : c + node_base; // (first + tri_base < 2^27: the host checks tri_end against kLeafFirstMask)
+}
+// One thread per (node, octant) of ONE mesh's region (in / abs_oct / wide point at the region's first node): the octant's copy of the quantised
+// node with absolute child references into `abs_oct`, and the same four references into PacketNode::pad of the packet form (which the
+// two-level kernels never read).  live (nullable): the tree's node count on the device; without it all n slots hold nodes (the host builder's count).
+__global__ void k_ss_expand(const Node4Q* __restrict__ in, Node4Q* __restrict__ abs_oct, PacketNode* __restrict__ wide, const uint32_t stride, const uint32_t n,
+                            const uint32_t* __restrict__ live, const uint32_t node_base, const uint32_t tri_base)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = g >> 3, oct = g & 7u;
+    if (i >= n || (live && i >= *live)) return;
+    Node4Q q = make_octant_node(in[i], oct);
+    for (int k = 0; k < 4; k++) q.child[k] = absolute_ref(q.child[k], node_base, tri_base);
+    abs_oct[(size_t)oct * stride + i] = q;
+    if (wide) *reinterpret_cast<uint4*>(wide[(size_t)oct * stride + i].pad) = make_uint4(q.child[0], q.child[1], q.child[2], q.child[3]);
+}
+// The graft of one TLAS: node i of the TLAS's 4-wide tree becomes node root + i of the mesh node arrays, with the same child boxes — an interior
+// child i' refers to root + i', a leaf of ONE instance to the root node of that instance's mesh, a leaf of several to a chain of extra nodes
+// (at root + n_nodes_max + the leaf's first slot in the instance list; up to four mesh roots per node, or three and the next node of the
+// chain, every child with the leaf's box: it contains every one of them).  One thread per TLAS node.
+__global__ void k_ss_graft(const Node4* __restrict__ raw, const uint32_t n_nodes_max, const uint32_t* __restrict__ live, const uint32_t* __restrict__ prims,
+                           const InstanceXform* __restrict__ xf, const uint32_t root, Node4Q* __restrict__ abs_oct, PacketNode* __restrict__ wide, const uint32_t stride)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes_max || i >= *live) return;
+    auto emit = [&](const Node4& n, const uint32_t at) {
+        const Node4Q q = quantize_node(n);
+        for (uint32_t oct = 0; oct < 8u; oct++) {
+            const Node4Q oq = make_octant_node(q, oct);
+            abs_oct[(size_t)oct * stride + at] = oq;
+            if (wide) {
+                PacketNode pn = make_packet_node(q, oct);
+                for (int k = 0; k < 4; k++) pn.pad[k] = pn.child[k];
+                wide[(size_t)oct * stride + at] = pn;
+            }
+        }
+    };
+    Node4 n = raw[i];
+    for (int c = 0; c < 4; c++) {
+        const uint32_t ref = n.child[c];
+        if (ref == kInvalidRef) continue;
+        if (!(ref & kLeafBit)) { n.child[c] = root + ref; continue; }
+        const uint32_t first = ref & kLeafFirstMask, count = ((ref >> 27) & 15u) + 1u;
+        if (count == 1u) { n.child[c] = xf[prims[first]].node_base; continue; }
+        const uint32_t chain = root + n_nodes_max + first;
+        n.child[c] = chain;
+        uint32_t left = count, pos = first, at = chain;
+        while (left > 0u) {
+            Node4 e;
+            const uint32_t here = left <= 4u ? left : 3u;
+            for (int k = 0; k < 4; k++) {
+                const bool used = (uint32_t)k < here || (k == 3 && left > 4u);
+                e.lox[k] = n.lox[c]; e.hix[k] = n.hix[c]; e.loy[k] = n.loy[c]; e.hiy[k] = n.hiy[c]; e.loz[k] = n.loz[c]; e.hiz[k] = n.hiz[c];
+                e.child[k] = !used ? kInvalidRef : ((uint32_t)k < here ? xf[prims[pos + k]].node_base : at + 1u);
+                e.pad[k] = 0u;
+            }
+            emit(e, at);
+            left -= here; pos += here; at++;
+        }
+    }
+    emit(n, root + i);
+}
+// the packets of one mesh name the mesh's one instance (TriPacket::pad; read by the single-space closest-hit kernels only)
+__global__ void k_ss_packet_ids(TriPacket* __restrict__ packets, const uint32_t n, const uint32_t gid)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) packets[i].pad = bitsf(gid);
+}
+
 // ---------------------------------------------------------------- launch wrappers
 static inline uint32_t ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 static inline dim3 xcd_grid(const uint32_t blocks) { return dim3((blocks + 511u) & ~511u); } // padded for xcd_block / xcd_run
@@ -1209,11 +1405,31 @@ void launch_tlas_finish(hipStream_t s, const Node4* raw, Node4Q* out, const Octa
     hipLaunchKernelGGL(k_tlas_finish, dim3(expand_blocks + prepare_blocks), dim3(256), 0, s, raw, out, oc.wide, oc.quant, oc.stride, n_nodes_max, live, expand_blocks, matrices,
                        mesh_of_instance, meshes, n_instances, xf, nm);
 }
+void launch_ss_expand(hipStream_t s, const Node4Q* in, Node4Q* abs_oct, PacketNode* wide, uint32_t stride, uint32_t n, const uint32_t* live, uint32_t node_base, uint32_t tri_base)
+{
+    if (n) hipLaunchKernelGGL(k_ss_expand, dim3(ceil_div((uint64_t)n * 8u, 256)), dim3(256), 0, s, in + node_base, abs_oct + node_base, wide ? wide + node_base : nullptr, stride, n, live,
+                              node_base, tri_base);
+}
+void launch_ss_graft(hipStream_t s, const Node4* raw, uint32_t n_nodes_max, const uint32_t* live, const uint32_t* prims, const InstanceXform* xf, uint32_t root, Node4Q* abs_oct,
+                     PacketNode* wide, uint32_t stride)
+{
+    if (n_nodes_max) hipLaunchKernelGGL(k_ss_graft, dim3(ceil_div(n_nodes_max, 64)), dim3(64), 0, s, raw, n_nodes_max, live, prims, xf, root, abs_oct, wide, stride);
+}
+void launch_ss_packet_ids(hipStream_t s, TriPacket* packets, uint32_t n, uint32_t gid)
+{
+    if (n) hipLaunchKernelGGL(k_ss_packet_ids, dim3(ceil_div(n, 256)), dim3(256), 0, s, packets, n, gid);
+}
 void launch_primary(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, bool count)
 {
     const dim3 grid = xcd_grid(ceil_div(p.capacity, kTraceBlock)), block(kTraceBlock);
     with_flag(count, [&](auto c) {
-        if ((cam.flags & kFlagPacketPrimary) && sc.tlas_wide && sc.blas_wide) hipLaunchKernelGGL(k_primary_packet<c.value>, grid, block, 0, s, cam, sc, p);
+        const bool packets = (cam.flags & kFlagPacketPrimary) && sc.tlas_wide && sc.blas_wide;
+        // (a launch's flavour is the scene's: wave-uniform by construction; counting frames take the counting twins, so the counters describe
+        // the kernels that are timed)
+        if (sc.ss_root) {
+            if (packets) hipLaunchKernelGGL(k_primary_packet_ss<c.value>, grid, block, 0, s, cam, sc, p);
+            else hipLaunchKernelGGL(k_primary_ss<c.value>, grid, block, 0, s, cam, sc, p);
+        } else if (packets) hipLaunchKernelGGL(k_primary_packet<c.value>, grid, block, 0, s, cam, sc, p);
         else hipLaunchKernelGGL(k_primary<c.value>, grid, block, 0, s, cam, sc, p);
     });
 }
@@ -1221,7 +1437,11 @@ void launch_primary_batch(hipStream_t s, const CameraParams& cam, const BatchVie
 {
     const dim3 grid = xcd_grid(ceil_div(p.capacity, kTraceBlock)), block(kTraceBlock);
     with_flag(count, [&](auto c) {
-        if ((cam.flags & kFlagPacketPrimary) && sc.tlas_wide && sc.blas_wide) hipLaunchKernelGGL(k_primary_batch_packet<c.value>, grid, block, 0, s, cam, views, sc, p);
+        const bool packets = (cam.flags & kFlagPacketPrimary) && sc.tlas_wide && sc.blas_wide;
+        if (sc.ss_root) {
+            if (packets) hipLaunchKernelGGL(k_primary_batch_packet_ss<c.value>, grid, block, 0, s, cam, views, sc, p);
+            else hipLaunchKernelGGL(k_primary_batch_ss<c.value>, grid, block, 0, s, cam, views, sc, p);
+        } else if (packets) hipLaunchKernelGGL(k_primary_batch_packet<c.value>, grid, block, 0, s, cam, views, sc, p);
         else hipLaunchKernelGGL(k_primary_batch<c.value>, grid, block, 0, s, cam, views, sc, p);
     });
 }
@@ -1229,7 +1449,10 @@ void launch_extend(hipStream_t s, const CameraParams& cam, const SceneDev& sc, c
 {
     const dim3 block(kTraceBlock);
     with_flag(count, [&](auto c) {
-        if (cam.stream_run) hipLaunchKernelGGL(k_extend_stream<c.value>, xcd_grid(ceil_div(p.capacity, kTraceBlock * cam.stream_run)), block, 0, s, cam, sc, p, bounce, order);
+        if (sc.ss_root) {
+            if (cam.stream_run) hipLaunchKernelGGL(k_extend_stream_ss<c.value>, xcd_grid(ceil_div(p.capacity, kTraceBlock * cam.stream_run)), block, 0, s, cam, sc, p, bounce, order);
+            else hipLaunchKernelGGL(k_extend_ss<c.value>, xcd_grid(ceil_div(p.capacity, kTraceBlock)), block, 0, s, cam, sc, p, bounce, order);
+        } else if (cam.stream_run) hipLaunchKernelGGL(k_extend_stream<c.value>, xcd_grid(ceil_div(p.capacity, kTraceBlock * cam.stream_run)), block, 0, s, cam, sc, p, bounce, order);
         else hipLaunchKernelGGL(k_extend<c.value>, xcd_grid(ceil_div(p.capacity, kTraceBlock)), block, 0, s, cam, sc, p, bounce, order);
     });
 }
@@ -1249,6 +1472,24 @@ void launch_shadow(hipStream_t s, const CameraParams& cam_in, const SceneDev& sc
     if (!packets_possible || (cam.flags & kFlagPacketShadow)) cam.flags &= ~kFlagPacketShadowFar;
     // worst case: every path pushed a shadow ray, every bucket padded to whole wavefronts
     const dim3 grid = xcd_grid(ceil_div(p.capacity, kTraceBlock) + kShadowBuckets), block(kTraceBlock);
+    if (sc.ss_root) { // the same launches, the single-space twins
+        with_flag(count, [&](auto c) {
+            if (packets_possible && (cam.flags & kFlagPacketShadow)) {
+                hipLaunchKernelGGL((k_shadow_packet_ss<c.value, true>), grid, block, 0, s, cam, sc, p, bounce);
+                hipLaunchKernelGGL((k_shadow_packet_ss<c.value, false>), grid, block, 0, s, cam, sc, p, bounce);
+                return;
+            }
+            if (cam.flags & kFlagPacketShadowFar) hipLaunchKernelGGL((k_shadow_packet_ss<c.value, true>), grid, block, 0, s, cam, sc, p, bounce);
+            if (cam.stream_run && bounce >= 1u) {
+                const dim3 stream_grid = xcd_grid(ceil_div(p.capacity, kTraceBlock * cam.stream_run) + kShadowBuckets);
+                hipLaunchKernelGGL((k_shadow_stream_ss<c.value, true>), stream_grid, block, 0, s, cam, sc, p, bounce);
+                hipLaunchKernelGGL((k_shadow_stream_ss<c.value, false>), stream_grid, block, 0, s, cam, sc, p, bounce);
+                return;
+            }
+            hipLaunchKernelGGL(k_shadow_ss<c.value>, grid, block, 0, s, cam, sc, p, bounce);
+        });
+        return;
+    }
     with_flag(count, [&](auto c) {
         if (packets_possible && (cam.flags & kFlagPacketShadow)) { // one launch per visiting order
             hipLaunchKernelGGL((k_shadow_packet<c.value, true>), grid, block, 0, s, cam, sc, p, bounce);

@@ -24,6 +24,8 @@
 //   * an instance whose inverse matrix is exactly the identity is entered without the matrix product;
 //   * the world-space ray is parked in LDS above the lane's stack column (6 words) and fetched back when an instance is entered or left;
 //   * pops of the any-hit loop read LDS with ds_read_b32 (the closest-hit loop keeps the flat load the compiler merges the two stack homes into);
+//   * a scene whose instances are ALL the exact identity, one per mesh, is not walked on two levels at all: the SS flavour below walks one tree
+//     in one space (DESIGN.md "Single-space scenes");
 //   * the loop's SHAPE per kind of ray: any hit and both streaming kinds FLAT (traverse_flat.inc), the plain closest hit NESTED (traverse_nested.inc).
 namespace rfwhip {
 
@@ -40,7 +42,6 @@ struct SceneView {
     const Node4Q* tlas_nodes;
     const uint32_t* tlas_prims; // instance ids in TLAS leaf order
     const InstanceXform* instances;
-    const Node4Q* blas_nodes;
     // the per-octant copies of both trees (make_octant_node: entry / exit planes picked, children front to back), copy `oct` of node i at
     // [oct * stride + i]: what the traversal below reads
     const Node4Q* tlas_oct;
@@ -52,6 +53,10 @@ struct SceneView {
     uint32_t spill_rows;        // rows of `spill` a lane may use (kStackSpill; a test option lowers it to exercise the overflow path)
     uint32_t* overflow_flag;    // pinned host word (mapped): set when a ray's stack would exceed LDS + spill rows
     QueueCounters* counters;
+    // single-space flavours (SS, below): blas_oct is then the copy of the mesh trees whose child references are ABSOLUTE (interior: index in the
+    // array, leaf: first packet in tri_packets) and ss_root the root of this frame's graft — a few nodes over the instances' world boxes whose
+    // leaves are the meshes' root nodes (DESIGN.md "Single-space scenes")
+    uint32_t ss_root;
 };
 
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -83,15 +88,22 @@ struct TravCounters {
 // t_min < t' < t.
 // FAR_FIRST (any hit only): hit children are visited in order of DECREASING EXIT distance (key = -exit instead of entry) — the search for an
 // occluder starts at the far end of the ray.  The triangle tests, and therefore the answer, are the same in either order.
-template <bool ANY_HIT, bool COUNT, bool FAR_FIRST = false>
+// SS (single space): the scene is one tree in world space (every instance exactly the identity, one per mesh): no TLAS, no change of space, no
+// parked ray; the instance of a hit comes from the triangle packet (TriPacket::pad).  The ray is canonicalised once, o = O + 0.0f, d = D + 0.0f:
+// what every entry into an identity instance computes in the two-level walk, so the triangle tests see the same numbers.
+template <bool ANY_HIT, bool COUNT, bool FAR_FIRST = false, bool SS = false>
 RFW_DI bool traverse(const SceneView& sc, const f3 O, const f3 D, const float t_min, float& t, float& hu, float& hv, int32_t& hit_inst,
                      int32_t& hit_tri, uint32_t* lds_stack, const uint32_t lane_slot, const uint32_t spill_base, TravCounters& tc)
 {
     constexpr int kStack = ANY_HIT ? kStackLdsAny : kStackLds; // LDS stack rows of this kernel flavour
     f3 o = O, d = D;
+    if constexpr (SS) {
+        o = mk3(O.x + 0.0f, O.y + 0.0f, O.z + 0.0f);
+        d = mk3(D.x + 0.0f, D.y + 0.0f, D.z + 0.0f);
+    }
     // the world-space ray is parked in LDS (6 words above the lane's stack column) and fetched back when an instance is entered or left, so
     // it does not occupy six registers through the whole loop (the closest-hit kernels spill at 6 waves per SIMD, the any-hit ones at 8)
-    {
+    if constexpr (!SS) {
         uint32_t* park = lds_stack + kStack * kTraceBlock + lane_slot;
         park[0] = fbits(O.x); park[kTraceBlock] = fbits(O.y); park[2 * kTraceBlock] = fbits(O.z);
         park[3 * kTraceBlock] = fbits(D.x); park[4 * kTraceBlock] = fbits(D.y); park[5 * kTraceBlock] = fbits(D.z);
@@ -109,11 +121,15 @@ RFW_DI bool traverse(const SceneView& sc, const f3 O, const f3 D, const float t_
     if (!((D.x == D.x) && (D.y == D.y) && (D.z == D.z) && (D.x != 0.0f || D.y != 0.0f || D.z != 0.0f))) return false;
     f3 inv = slab_inv(d);
     int sp = 0;
+    // COUNT && SS: the stack height below which every entry was pushed by a graft node (set behind a graft node's pushes, lowered by every pop
+    // below it): an interior entry popped from there that lies below the graft is a mesh's root about to be visited ("instances entered")
+    int gtop = 0;
     int blas_sp = -1;          // stack height at BLAS entry; -1 = currently in the TLAS
     int32_t cur_inst = -1;
     uint32_t tri_base = 0;
-    uint32_t cur = 0;          // TLAS root (interior ref 0)
-    const Node4Q* nodes = space_nodes(sc, false, 0u, inv); // node array of the current space (TLAS, or the entered instance's BLAS)
+    uint32_t cur = SS ? sc.ss_root : 0u; // TLAS root (interior ref 0) / the graft's root
+    // node array of the current space (TLAS, or the entered instance's BLAS; SS: the one array, for good)
+    const Node4Q* nodes = SS ? sc.blas_oct + (size_t)octant_bits(inv) * sc.blas_oct_stride : space_nodes(sc, false, 0u, inv);
 
     // pops of the any-hit kernel read LDS with ds_read_b32 (measured +0.7 % frame rate); the closest-hit kernels keep the flat load the
     // compiler builds, because every other formulation of their pop tried (ds_read, top of stack in a register) changed their loop nest
@@ -139,6 +155,12 @@ RFW_DI bool traverse(const SceneView& sc, const f3 O, const f3 D, const float t_
         }
         sp++;
     };
+    auto count_root = [&](const uint32_t v) { // (called by pop() with sp already lowered to the entry's slot)
+        if (sp < gtop) {
+            gtop = sp;
+            if (!(v & kLeafBit) && v < sc.ss_root) tc.insts++;
+        }
+    };
     auto pop = [&]() -> uint32_t {
         sp--;
         if (kDsPop) {
@@ -150,6 +172,12 @@ RFW_DI bool traverse(const SceneView& sc, const f3 O, const f3 D, const float t_
                 v = sc.spill[(size_t)(sp - kStack) * sc.spill_stride + spill_slot()];
                 asm volatile("" : "+v"(v)); // the merged value is not a load: keeps the compiler from folding both loads into one flat load again
             }
+            if constexpr (COUNT && SS) count_root(v);
+            return v;
+        }
+        if constexpr (COUNT && SS) {
+            const uint32_t v = sp < kStack ? lds_stack[sp * kTraceBlock + lane_slot] : sc.spill[(size_t)(sp - kStack) * sc.spill_stride + spill_slot()];
+            count_root(v);
             return v;
         }
         if (sp < kStack) return lds_stack[sp * kTraceBlock + lane_slot];
@@ -190,7 +218,7 @@ RFW_DI bool traverse(const SceneView& sc, const f3 O, const f3 D, const float t_
 //   st.more()                 wave-uniform: the run has entries left
 //   st.fetch(idle, O, D, t)   the calling lanes (all idle) take the next entries; false for a lane that gets none (Stream::kTMin: the queue's t_min)
 //   st.commit(occluded, t, hu, hv, hit_inst, hit_tri)   the calling lane's finished ray
-template <bool ANY_HIT, bool COUNT, bool FAR_FIRST, class Stream>
+template <bool ANY_HIT, bool COUNT, bool FAR_FIRST, bool SS = false, class Stream = void>
 RFW_DI void traverse_stream(const SceneView& sc, Stream& st, const uint32_t refill, const uint32_t leaf_gate, uint32_t* lds_stack, const uint32_t lane_slot, const uint32_t spill_base,
                             TravCounters& tc)
 {
@@ -209,6 +237,9 @@ RFW_DI void traverse_stream(const SceneView& sc, Stream& st, const uint32_t refi
     };
     f3 inv = mk3(0.0f);
     int sp = 0;
+    // COUNT && SS: the stack height below which every entry was pushed by a graft node (set behind a graft node's pushes, lowered by every pop
+    // below it): an interior entry popped from there that lies below the graft is a mesh's root about to be visited ("instances entered")
+    int gtop = 0;
     int blas_sp = -1;
     int32_t cur_inst = -1;
     uint32_t tri_base = 0;
@@ -232,6 +263,12 @@ RFW_DI void traverse_stream(const SceneView& sc, Stream& st, const uint32_t refi
         }
         sp++;
     };
+    auto count_root = [&](const uint32_t v) { // (called by pop() with sp already lowered to the entry's slot)
+        if (sp < gtop) {
+            gtop = sp;
+            if (!(v & kLeafBit) && v < sc.ss_root) tc.insts++;
+        }
+    };
     auto pop = [&]() -> uint32_t {
         sp--;
         if (kDsPop) {
@@ -240,6 +277,12 @@ RFW_DI void traverse_stream(const SceneView& sc, Stream& st, const uint32_t refi
                 v = sc.spill[(size_t)(sp - kStack) * sc.spill_stride + spill_slot()];
                 asm volatile("" : "+v"(v));
             }
+            if constexpr (COUNT && SS) count_root(v);
+            return v;
+        }
+        if constexpr (COUNT && SS) {
+            const uint32_t v = sp < kStack ? lds_stack[sp * kTraceBlock + lane_slot] : sc.spill[(size_t)(sp - kStack) * sc.spill_stride + spill_slot()];
+            count_root(v);
             return v;
         }
         if (sp < kStack) return lds_stack[sp * kTraceBlock + lane_slot];
@@ -267,17 +310,21 @@ RFW_DI void traverse_stream(const SceneView& sc, Stream& st, const uint32_t refi
                     const bool got_ = st.fetch(idle, o, d, t);                                                                        \
                     cur = kIdleRef;                                                                                                   \
                     if (got_) {                                                                                                       \
-                        {   /* the fetched ray lands in the traversal's own registers and is parked at once */                         \
+                        if constexpr (SS) {                                                                                           \
+                            o = mk3(o.x + 0.0f, o.y + 0.0f, o.z + 0.0f);                                                              \
+                            d = mk3(d.x + 0.0f, d.y + 0.0f, d.z + 0.0f);                                                              \
+                        } else {   /* the fetched ray lands in the traversal's own registers and is parked at once */                  \
                             uint32_t* park = lds_stack + kStack * kTraceBlock + lane_slot;                                            \
                             park[0] = fbits(o.x); park[kTraceBlock] = fbits(o.y); park[2 * kTraceBlock] = fbits(o.z);                 \
                             park[3 * kTraceBlock] = fbits(d.x); park[4 * kTraceBlock] = fbits(d.y); park[5 * kTraceBlock] = fbits(d.z); \
                         }                                                                                                             \
                         inv = slab_inv(d);                                                                                            \
-                        sp = 0; blas_sp = -1; cur_inst = -1; tri_base = 0; nodes = space_nodes(sc, false, 0u, inv);                   \
+                        sp = 0; gtop = 0; blas_sp = -1; cur_inst = -1; tri_base = 0;                                                  \
+                        nodes = SS ? sc.blas_oct + (size_t)octant_bits(inv) * sc.blas_oct_stride : space_nodes(sc, false, 0u, inv);   \
                         hu = 0.0f; hv = 0.0f; hit_inst = -1; hit_tri = -1; occ_ = 0u;                                                 \
                         /* a degenerate direction hits nothing (see traverse()): finished before it starts */                          \
                         const bool fine_ = ((d.x == d.x) && (d.y == d.y) && (d.z == d.z) && (d.x != 0.0f || d.y != 0.0f || d.z != 0.0f)); \
-                        cur = fine_ ? 0u : kDoneRef;                                                                                  \
+                        cur = fine_ ? (SS ? sc.ss_root : 0u) : kDoneRef;                                                              \
                     }                                                                                                                 \
                 }                                                                                                                     \
                 st.advance(idle);                                                                                                     \

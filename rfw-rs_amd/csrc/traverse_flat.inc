@@ -22,12 +22,12 @@
         if ((int32_t)cur >= 0) {
 #include "traverse_node.inc"
         }
-        if (leaf_trip_ && (((int32_t)cur < -3) & (blas_sp >= 0))) {
+        if (leaf_trip_ && (((int32_t)cur < -3) & (SS || blas_sp >= 0))) {
             uint32_t next_ = kInvalidRef;
 #include "traverse_leaf.inc"
             cur = next_;
         }
-        if (tlas_trip_ && (((int32_t)cur < -3) & (blas_sp < 0))) {
+        if constexpr (!SS) if (tlas_trip_ && (((int32_t)cur < -3) & (blas_sp < 0))) {
             // ---- TLAS leaf: the first instance is entered below, the rest of the list stays on the stack
             const uint32_t first = cur & kLeafFirstMask, count = ((cur >> 27) & 15u) + 1u;
             if (count > 1) push(make_leaf(first + 1, count - 1));
@@ -37,7 +37,11 @@
         // ---- a change of space (into the instance just found / back to the world when its tree is exhausted) happens in ONE place: the ray,
         // its reciprocal and the node array have a single definition per trip (two made the compiler carry a second copy of all of them
         // around the loop: 24 v_mov per trip)
-        {
+        if constexpr (SS) { // one space: nothing to enter or leave, only the next stack entry
+            const bool next_entry_ = cur == kInvalidRef, last_ = next_entry_ & (sp == 0);
+            if (next_entry_ & !last_) cur = pop();
+            cur = last_ ? kDoneRef : cur;
+        } else {
             const bool enter = enter_gid != kInvalidRef;
             const bool leave = (cur == kInvalidRef) & (blas_sp >= 0) & (sp == blas_sp);
             if (enter | leave) {

@@ -27,12 +27,13 @@
                     if (ok & (tt > t_min) & (tt < t)) { RFW_TRAV_OCCLUDED }
                 } else {
                     const int32_t prim = (int32_t)fbits(p0.w);
-                    const bool lower = (cur_inst < hit_inst) | ((cur_inst == hit_inst) & (prim < hit_tri));
+                    const int32_t inst_ = SS ? (int32_t)fbits(p2.w) : cur_inst; // (SS: the packet names its mesh's one instance)
+                    const bool lower = (inst_ < hit_inst) | ((inst_ == hit_inst) & (prim < hit_tri));
                     const bool take = ok & (tt > t_min) & ((tt < t) | ((tt == t) & (hit_inst >= 0) & lower));
                     t = take ? tt : t;
                     hu = take ? u * p1.w : hu;
                     hv = take ? v * p1.w : hv;
-                    hit_inst = take ? cur_inst : hit_inst;
+                    hit_inst = take ? inst_ : hit_inst;
                     hit_tri = take ? prim : hit_tri;
                 }
             }

@@ -3,10 +3,10 @@
     for (;;) {
         if (!(cur & kLeafBit)) {
 #include "traverse_node.inc"
-        } else if (blas_sp >= 0) {
+        } else if (SS || blas_sp >= 0) {
 #include "traverse_leaf.inc"
             cur = kInvalidRef;
-        } else {
+        } else if constexpr (!SS) {
             // ---- TLAS leaf: enter the first instance, keep the rest of the list on the stack
             const uint32_t first = cur & kLeafFirstMask, count = ((cur >> 27) & 15u) + 1u;
             if (count > 1) push(make_leaf(first + 1, count - 1));
@@ -34,7 +34,7 @@
             continue;
         }
         // ---- next entry
-        if (blas_sp >= 0 && sp == blas_sp) { // BLAS exhausted: back to world space
+        if (!SS && blas_sp >= 0 && sp == blas_sp) { // BLAS exhausted: back to world space
             blas_sp = -1;
             o = world_o();
             d = world_d();

@@ -55,4 +55,5 @@
                 if (kFwd) { if (hit[0]) push(ch.x); if (hit[1]) push(ch.y); if (hit[2]) push(ch.z); if (hit[3]) push(ch.w); }
                 else { if (hit[3]) push(ch.w); if (hit[2]) push(ch.z); if (hit[1]) push(ch.y); if (hit[0]) push(ch.x); }
             }
+            if (COUNT && SS && cur >= sc.ss_root) gtop = sp; // a graft node: what lies on the stack now are graft nodes and meshes' roots (traverse.h, count_root)
             cur = kInvalidRef; // (falls through to the pop below)

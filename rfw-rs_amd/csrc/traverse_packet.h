@@ -86,7 +86,9 @@ template <bool MASK> RFW_DI void slab4(const su16 a, const su16 b, const SlabRay
 
 // ANY_HIT = false: t / hu / hv / hit_inst / hit_tri of every active lane describe its nearest accepted hit.  ANY_HIT = true: `occluded` per lane.
 // Called by ALL 64 lanes of the wavefront in uniform control flow; `active` says which of them carry a ray.
-template <bool ANY_HIT, bool COUNT, bool FAR_FIRST = false>
+// SS (single space, traverse.h): blas_wide's nodes carry ABSOLUTE child references in PacketNode::pad and sc.ss_root is the graft's root: the
+// packet walks one tree in one space — no TLAS step, no instance record, the ray's slab form and the octant groups made once.
+template <bool ANY_HIT, bool COUNT, bool FAR_FIRST = false, bool SS = false>
 RFW_DI void traverse_packet(const SceneView& sc, const PacketNode* __restrict__ tlas_wide, const uint32_t tlas_stride, const PacketNode* __restrict__ blas_wide,
                             const uint32_t blas_stride, const bool active, const f3 O, const f3 D, const float t_min, float& t, float& hu, float& hv, int32_t& hit_inst, int32_t& hit_tri, bool& occluded,
                             TravCounters& tc)
@@ -98,7 +100,8 @@ RFW_DI void traverse_packet(const SceneView& sc, const PacketNode* __restrict__ 
     const bool sane = (D.x == D.x) && (D.y == D.y) && (D.z == D.z) && (D.x != 0.0f || D.y != 0.0f || D.z != 0.0f);
     uint64_t todo = ballot64(active && sane);
     const uint32_t lane_id = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const uint32_t world_oct = octant_of(slab_inv(D));
+    // (SS: the octant of the canonical direction D + 0.0f, the one the ray keeps)
+    const uint32_t world_oct = SS ? octant_of(slab_inv(mk3(D.x + 0.0f, D.y + 0.0f, D.z + 0.0f))) : octant_of(slab_inv(D));
     if (COUNT && active) tc.nodes++; // the root
     // the wavefront's rays by world-space octant: inside a group the near / far plane of every axis is a wave-uniform choice
     while (todo != 0ull) {
@@ -107,11 +110,11 @@ RFW_DI void traverse_packet(const SceneView& sc, const PacketNode* __restrict__ 
         todo &= ~group;
         uint64_t live = group;               // lanes whose votes count (any hit: minus the rays that have found their occluder)
         uint64_t later = 0ull;               // lanes that wait to enter the current instance with another object-space octant
-        uint32_t sp = 0u;
+        uint32_t sp = 0u, gtop = 0u;
         uint32_t blas_sp = 0u;               // stack height at BLAS entry
-        bool in_blas = false;
+        bool in_blas = SS;                   // (SS: the one space counts as a mesh's: its leaves hold triangles)
         uint32_t inst_first = 0u;            // the instance being traversed: its slot in the TLAS leaf list
-        uint32_t cur = 0u;                   // TLAS root
+        uint32_t cur = SS ? sc.ss_root : 0u; // TLAS root / the graft's root
         // ---- one pass of this loop per SPACE the packet is in: the rays' coordinates change only here, never inside the traversal loop
         for (;;) {
             f3 o = O, d = D;
@@ -120,7 +123,11 @@ RFW_DI void traverse_packet(const SceneView& sc, const PacketNode* __restrict__ 
             uint32_t tri_base = 0u;
             int32_t cur_inst = -1;
             uint64_t packet = live;
-            if (in_blas) {
+            if constexpr (SS) {
+                o = mk3(O.x + 0.0f, O.y + 0.0f, O.z + 0.0f);
+                d = mk3(D.x + 0.0f, D.y + 0.0f, D.z + 0.0f);
+                nodes = blas_wide + (size_t)goct * blas_stride;
+            } else if (in_blas) {
                 // enter the instance with the waiting lanes whose object-space octant is the first such lane's; the others wait in `later`
                 const uint32_t gid = *((scalar_ptr1)(uintptr_t)(sc.tlas_prims + inst_first));
                 const su16 xf = *((scalar_ptr16)(uintptr_t)(sc.instances + gid));
@@ -162,14 +169,24 @@ RFW_DI void traverse_packet(const SceneView& sc, const PacketNode* __restrict__ 
             const uint32_t floor_sp = in_blas ? blas_sp : 0u; // stack height at which this space is exhausted
             // next entry off the shared stack (kInvalidRef: the space is exhausted); an empty slot that was pushed (a NaN corner of the slab
             // test) comes back as kInvalidRef and is skipped
+            // COUNT && SS ("instances entered" = visits of a mesh's root by the packet's rays): gtop is the stack height below which every entry was
+            // pushed by a graft node — set behind a graft node's pushes, lowered by every pop below it
+            auto count_root = [&]() {
+                if (sp < gtop) {
+                    gtop = sp;
+                    if (!(cur & kLeafBit) && cur < sc.ss_root && in_mask(packet)) tc.insts++;
+                }
+            };
             auto pop = [&]() {
                 cur = kInvalidRef;
                 if (sp != floor_sp) {
                     sp--;
                     cur = lane_read(stack, sp);
+                    if constexpr (COUNT && SS) count_root();
                     while (__builtin_expect(cur == kInvalidRef && sp != floor_sp, 0)) { // (an empty slot somebody voted for: a NaN corner of the slab test; lanes outside the packet no longer produce one)
                         sp--;
                         cur = lane_read(stack, sp);
+                        if constexpr (COUNT && SS) count_root();
                     }
                 }
             };
@@ -183,7 +200,7 @@ RFW_DI void traverse_packet(const SceneView& sc, const PacketNode* __restrict__ 
                     const su16 a = np[0], b = np[1];
                     uint64_t m[4];
                     slab4<!kNanMask>(a, b, r, t, packet, m);
-                    const uint32_t c[4] = {b[8], b[9], b[10], b[11]};
+                    const uint32_t c[4] = {SS ? b[12] : b[8], SS ? b[13] : b[9], SS ? b[14] : b[10], SS ? b[15] : b[11]};
                     if (COUNT) {
                         // per lane: the nodes and triangles a traversal of its own would go on to visit (the children whose boxes IT hits)
 #pragma unroll
@@ -209,8 +226,12 @@ RFW_DI void traverse_packet(const SceneView& sc, const PacketNode* __restrict__ 
                         asm("s_cmp_lg_u64 %1, 0\n\ts_addc_u32 %0, %0, 0" : "+s"(sp) : "s"(m[i]) : "scc"); // sp += (m[i] != 0), on the scalar unit (the compiler converts the bool on the vector unit)
                     }
                     constexpr int kFirst = (ANY_HIT && FAR_FIRST) ? 3 : 0;
-                    if (m[kFirst] != 0ull) cur = c[kFirst];
-                    else pop();
+                    const bool graft_node = COUNT && SS && cur >= sc.ss_root;
+                    if (graft_node) gtop = sp;
+                    if (m[kFirst] != 0ull) {
+                        cur = c[kFirst];
+                        if (graft_node && !(cur & kLeafBit) && cur < sc.ss_root && in_mask(packet)) tc.insts++; // (a mesh's root taken without a trip over the stack)
+                    } else pop();
                 }
                 if (cur == kInvalidRef) { // the space is exhausted
                     if (in_blas) leave = true;
@@ -240,12 +261,13 @@ RFW_DI void traverse_packet(const SceneView& sc, const PacketNode* __restrict__ 
                             occluded = occluded | (ok & (tt > t_min) & (tt < t));
                         } else {
                             const int32_t prim = (int32_t)q0.w;
-                            const bool lower = (cur_inst < hit_inst) | ((cur_inst == hit_inst) & (prim < hit_tri));
+                            const int32_t inst_ = SS ? (int32_t)q2.w : cur_inst; // (SS: the packet names its mesh's one instance)
+                            const bool lower = (inst_ < hit_inst) | ((inst_ == hit_inst) & (prim < hit_tri));
                             const bool take = ok & (tt > t_min) & ((tt < t) | ((tt == t) & (hit_inst >= 0) & lower));
                             t = take ? tt : t;
                             hu = take ? u * bitsf(q1.w) : hu;
                             hv = take ? v * bitsf(q1.w) : hv;
-                            hit_inst = take ? cur_inst : hit_inst;
+                            hit_inst = take ? inst_ : hit_inst;
                             hit_tri = take ? prim : hit_tri;
                         }
                     }
@@ -258,7 +280,7 @@ RFW_DI void traverse_packet(const SceneView& sc, const PacketNode* __restrict__ 
                 }
                 pop();
             }
-            if (finished) break;
+            if (finished || (SS && leave)) break; // (SS: there is no space to go back to)
             if (leave) {
                 // out of the instance (exhausted, or nobody left to look): unwind to the entry height; lanes of another octant enter next
                 sp = blas_sp;
