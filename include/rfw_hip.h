@@ -290,7 +290,15 @@ RFW_HIP_API int rfw_hip_synchronize(void* instance);
  * previous image counts only where it shows the same instance.  An instance that is new, was removed in the previous image, changed its
  * mesh or has a matrix whose last row is not (0, 0, 0, 1) starts without history.  With one instance in the scene, and whenever no matrix
  * changes, the frame equals the one with the option off bit for bit.  A different value drops the history and starts a new image.  Skinned
- * meshes follow their instance matrix only.  Off, nothing is allocated, launched or written for it. */
+ * meshes follow their instance matrix only, unless "denoise_deform" is on.  Off, nothing is allocated, launched or written for it.
+ * Option "denoise_deform" = 0 (off, the default) | 1: where "denoise_motion" = 1 acts, and only there, a pixel whose primary hit lies on a
+ * skinned copy (an instance with a live skin) is reprojected through the pose its triangle had in the previous image: the hit's triangle
+ * and barycentrics give the point w v0' + u v1' + v v2' on the previous image's mesh-space vertices, which the previous instance matrix
+ * carries into the previous image's world, and the previous geometric normal likewise (DESIGN.md "Denoiser: deforming meshes"); from there
+ * the formula is "denoise_motion"'s.  An instance that gains or loses its skin, or whose skinned copy changes its mesh or triangle count,
+ * starts without history.  Without a skinned copy in the scene the frame equals the one with the option off bit for bit.  A different value
+ * drops the history and starts a new image; any other value is RFW_HIP_E_INVALID.  Out of scope: morph targets, vertices moved by
+ * rfw_hip_set_3d_mesh re-sends, camera-ray jitter.  Off, nothing is allocated, launched or written for it. */
 enum {
     RFW_HIP_RENDER_DEFAULT = 0,
     RFW_HIP_RENDER_NORMAL = 1,
@@ -330,7 +338,8 @@ RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
  *                  "texture_array" (gpu-rt's 1024^2 x 5 texture array, default 1), "ao_samples" / "ao_radius" (render modes 5, 6),
  *                  "denoise" 0 (off, default) | 1 ... 5 a-trous passes over the path-traced frame, "denoise_colour" (> 0),
  *                  "denoise_temporal" 0 (off, default) | 1 ... 64 samples of history across images, "denoise_motion" 0 (off, default) | 1
- *                  the history follows moving instances, "sample_offset" 0 (default) ... 2^24, the first sample index of every
+ *                  the history follows moving instances, "denoise_deform" 0 (off, default) | 1 the history follows skinned meshes,
+ *                  "sample_offset" 0 (default) ... 2^24, the first sample index of every
  *                  image — any other value of these is RFW_HIP_E_INVALID; see rfw_hip_render; "scale_filter" 0 nearest | 1 (default)
                   bilinear / area: how the render-size frame becomes the window-size one (see rfw_hip_create); the display transform:
  *                  "tonemap" 0 (off, default) | 1 | 2 | 3, "exposure", "tonemap_white", "auto_exposure" 0 | 1, "exposure_key",
@@ -460,7 +469,17 @@ RFW_HIP_API int rfw_hip_occludes4(void* instance, const float* origin_xyz4, cons
  * "dn_motion" (option "denoise_motion"): the records the latest temporal frame used, one of 96 bytes per instance id of that frame: the
  * rows of A = M' inverse(M) (3 x 4 floats: a point of this image -> the same point of the instance in the previous image), then the rows
  * of B = transpose(inverse(A)) (3 x 4 floats, of which [0][3] holds the uint32 state — 0 no history, 1 the matrix did not change, 2 moved —
- * and [1][3], [2][3] are 0).  A and B are zero where the state is 0.
+ * and [1][3], [2][3] are 0).  A and B are zero where the state is 0.  With option "denoise_deform" the state may be 3 (a skinned copy in
+ * both images): A then holds the rows of the previous forward matrix M' and B the rows of the previous transpose(inverse(M')).
+ * "dn_tris" (option "denoise_deform"): width * height pairs of uint32 of the current frame slot, per frame pixel the row of the device
+ * triangle buffer ("triangles") of the latest sample's primary hit, with bit 31 set iff the geometric normal was negated to face the camera,
+ * and the hit's packed 16-bit barycentrics (u in the low half, v in the high half); (0xffffffff, 0) where the camera ray missed; nothing
+ * before the first frame with the option on, after rfw_hip_resize, or once the option is off.
+ * "dn_pose" (option "denoise_deform"): the pose snapshot the latest temporal frame wrote, whichever slot ran it: four uint32 (n = the
+ * instance ids of that frame, T = the triangles of its skinned copies, 0, 0), then n records of four uint32 (the first "triangles" row of
+ * the instance's skinned copy, its triangle count, its first triangle in the snapshot, 0; all 0 for an instance that is no skinned copy),
+ * then T records of four float4: rows 0-3 of the copy's triangle records (vertex 0, 1, 2 with their w words, the geometric normal).
+ * Nothing unless the latest temporal frame ran with the option.
  * "ov_prims" (the 2D layer): one record of 48 bytes per primitive of the latest frame's 2D layer, in draw order: int32 X[3], Y[3] (the
  * snapped vertices, 8 sub-pixel bits, in the caller's vertex order; 0 where a vertex had no pixel position: w <= 0, not finite, too far), uint32 mesh, instance, triangle,
  * dropped (0 or 1), two pad words; nothing when the latest frame drew no 2D layer.  "ov_stats": three uint32 of that frame: primitives

@@ -611,3 +611,23 @@ class HipBackend:
         r = np.frombuffer(raw, np.float32).reshape(-1, 6, 4)
         state = np.frombuffer(raw, np.uint32).reshape(-1, 24)[:, 15].copy()
         return r[:, :3, :].copy(), r[:, 3:, :3].copy(), state
+
+    def denoise_tris(self):
+        """The triangles of the latest frame's primary hits (option "denoise_deform"): (H, W, 2) uint32 = (row of the device triangle buffer
+        with bit 31 set where the geometric normal was negated to face the camera, the hit's packed 16-bit barycentrics u | v << 16);
+        (0xffffffff, 0) where the camera ray missed; empty before the first frame with the option on."""
+        g = np.frombuffer(self.debug_read("dn_tris", 8 * self.render_width * self.render_height).tobytes(), np.uint32)
+        return g.reshape(-1, self.render_width, 2)
+
+    def denoise_pose(self):
+        """The pose snapshot the latest temporal frame wrote (option "denoise_deform"): (table, pose) with table (n, 3) uint32 per instance id
+        of that frame = (first row of its skinned copy in the triangle buffer, its triangles, its first triangle in `pose`), zeros for an
+        instance that is no skinned copy, and pose (T, 4, 4) float32 = rows 0-3 of the triangle records of every skinned copy (the mesh-space
+        vertices with their w words, the geometric normal); two empty arrays before the first such frame."""
+        raw = self.debug_read("dn_pose", 1 << 28).tobytes()
+        if len(raw) < 16:
+            return np.zeros((0, 3), np.uint32), np.zeros((0, 4, 4), np.float32)
+        n, t = (int(v) for v in np.frombuffer(raw[:16], np.uint32)[:2])
+        table = np.frombuffer(raw[16:16 + 16 * n], np.uint32).reshape(n, 4)[:, :3].copy()
+        pose = np.frombuffer(raw[16 + 16 * n:16 + 16 * n + 64 * t], np.float32).reshape(t, 4, 4).copy()
+        return table, pose

@@ -308,6 +308,9 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
         HIP_TRY(I, I->d_dn_ids.ensure(px));
         for (int q = 0; q < 2; q++) HIP_TRY(I, O->d_dn_history_ids[q].ensure(px));
     }
+    // option "denoise_deform": acts where the motion option does
+    const bool dnd = dnm && O->denoise_deform > 0;
+    if (dnd) HIP_TRY(I, I->d_dn_tris.ensure((size_t)I->width * I->height));
 
     // The 2D layer: where the frame is de-tiled on this device and the call leaves one image of rfw_hip_render behind, the draws of the last
     // synchronize() go over the finalised frame.  Nothing to draw, or no view_2d: no launch, no allocation, no wait.
@@ -423,6 +426,7 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
                 }
                 launch_dn_guide(st[s], cam[s], sc[s], g, I->d_dn_guide.ptr, k > 1 ? 0x00ffffffu : 0xffffffffu);
                 if (dnm) launch_dn_ids(st[s], cam[s], g, I->d_dn_ids.ptr, k > 1 ? 0x00ffffffu : 0xffffffffu);
+                if (dnd) launch_dn_tris(st[s], cam[s], sc[s], g, I->d_dn_tris.ptr, k > 1 ? 0x00ffffffu : 0xffffffffu);
             }
         }
         for (uint32_t s = 0; s < S; s++) {
@@ -480,13 +484,41 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
                 const float v[12] = {view.pos.x, view.pos.y, view.pos.z, view.p1.x, view.p1.y, view.p1.z, view.right.x, view.right.y, view.right.z, view.up.x, view.up.y, view.up.z};
                 std::memcpy(O->dn_view[h], v, sizeof(v));
                 DnMotionLaunch ml{};
+                DnDeformLaunch dl{};
                 if (dnm) { // the snapshot of the TLAS this frame traced with, and the records against the previous image's
                     Instance* const T = tlas_of(I);
                     const uint32_t n_inst = (uint32_t)T->n_instances;
                     HIP_TRY(I, O->d_dn_snapshot[h].ensure(std::max<size_t>(n_inst, 1) * kDnInstanceBytes));
                     HIP_TRY(I, O->d_dn_motion.ensure(std::max<size_t>(n_inst, 1) * kDnMotionBytes));
+                    DnDeformMotion dm{};
+                    if (dnd) { // the skinned copies of the scene this frame traced (they change only with a synchronize(), which drains the frames in flight)
+                        std::vector<uint4> copies;
+                        uint32_t total = 0;
+                        for (const auto& kv : O->derived) {
+                            const MeshRecord& r = O->mesh_records[kv.second.record];
+                            copies.push_back(make_uint4(r.tri_base, r.tri_count, total, kv.second.record));
+                            total += r.tri_count;
+                        }
+                        if (copies.size() != O->dn_copies.size() || (!copies.empty() && std::memcmp(copies.data(), O->dn_copies.data(), copies.size() * sizeof(uint4)) != 0)) {
+                            HIP_TRY(I, O->d_dn_copies.ensure(copies.size()));
+                            O->dn_copies = copies; // (the copy reads the owner's vector, which stays as it is until the table changes again)
+                            if (!copies.empty()) HIP_TRY(I, hipMemcpyAsync(O->d_dn_copies.ptr, O->dn_copies.data(), copies.size() * sizeof(uint4), hipMemcpyHostToDevice, main));
+                        }
+                        HIP_TRY(I, O->d_dn_refs[h].ensure(std::max<size_t>(n_inst, 1)));
+                        if (total) HIP_TRY(I, O->d_dn_pose[h].ensure(4 * (size_t)total));
+                        O->dn_pose_tris[h] = total;
+                        dm.copies = O->d_dn_copies.ptr;
+                        dm.n_copies = (uint32_t)copies.size();
+                        dm.prev_refs = I->dn_image ? O->d_dn_refs[h ^ 1u].ptr : nullptr;
+                        dm.cur_refs = O->d_dn_refs[h].ptr;
+                        launch_dn_pose(main, sc[0].triangles, O->d_dn_copies.ptr, dm.n_copies, total, O->d_dn_pose[h].ptr);
+                        dl.tris = I->d_dn_tris.ptr;
+                        dl.refs = O->d_dn_refs[h].ptr;
+                        dl.prev_refs = dm.prev_refs;
+                        dl.prev_pose = I->dn_image ? O->d_dn_pose[h ^ 1u].ptr : nullptr;
+                    }
                     launch_dn_motion(main, T->d_forward, T->d_xforms.ptr, T->d_normals.ptr, n_inst, I->dn_image ? O->d_dn_snapshot[h ^ 1u].ptr : nullptr,
-                                     O->dn_snap_count[h ^ 1u], O->d_dn_snapshot[h].ptr, O->d_dn_motion.ptr);
+                                     O->dn_snap_count[h ^ 1u], O->d_dn_snapshot[h].ptr, O->d_dn_motion.ptr, dnd ? &dm : nullptr);
                     O->dn_snap_count[h] = O->dn_motion_count = n_inst;
                     ml.ids = I->d_dn_ids.ptr;
                     ml.prev_ids = I->dn_image ? O->d_dn_history_ids[h ^ 1u].ptr : nullptr;
@@ -495,8 +527,9 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
                     ml.n_records = n_inst;
                 }
                 launch_dn_temporal(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_dn_guide.ptr, I->dn_image ? O->d_dn_history[h ^ 1u].ptr : nullptr, O->d_dn_history[h].ptr,
-                                   O->dn_view[h ^ 1u], I->sample_count, O->denoise_temporal, dnm ? &ml : nullptr);
+                                   O->dn_view[h ^ 1u], I->sample_count, O->denoise_temporal, dnm ? &ml : nullptr, dnd ? &dl : nullptr);
                 O->dn_latest = h;
+                O->dn_deform_latest = dnd;
                 x0 = O->d_dn_history[h].ptr;
             }
             launch_atrous(main, cam[0], I->d_acc_slab.ptr, I->cap_v, I->d_dn_guide.ptr, planes, I->d_frame_out.ptr, I->sample_count, I->denoise, I->denoise_colour,
@@ -773,6 +806,7 @@ void rfw_hip_destroy(void* inst)
         I->d_dn_history[0].release(); I->d_dn_history[1].release();
         I->d_dn_ids.release(); I->d_dn_motion.release();
         for (int q = 0; q < 2; q++) { I->d_dn_history_ids[q].release(); I->d_dn_snapshot[q].release(); }
+        I->release_deform();
         if (I->dn_chain) (void)hipEventDestroy(I->dn_chain);
         I->d_disp_state.release(); I->d_disp_hist.release();
         if (I->disp_chain) (void)hipEventDestroy(I->disp_chain);
@@ -891,6 +925,7 @@ int rfw_hip_resize(void* inst, uint32_t w, uint32_t h, double scale)
     I->d_dn_ids.release(); I->d_dn_motion.release();
     for (int q = 0; q < 2; q++) { I->d_dn_history_ids[q].release(); I->d_dn_snapshot[q].release(); I->dn_snap_count[q] = 0; }
     I->dn_motion_count = 0;
+    I->release_deform(); // option "denoise_deform": and the triangle plane, the pose snapshots and their tables
     I->disp_have_state = false; I->disp_latest = 0; // the display transform adapted to frames of the old size
     I->ov_frame_prims = I->ov_frame_words = 0; // the 2D layer's taps describe a frame of the old size
     // a gathered frame not de-tiled yet belongs to the old size (and d_recv may move below): forget it (each slot passes here for itself)
@@ -997,6 +1032,16 @@ int rfw_hip_set_option(void* inst, const char* key, double value)
         if (value != 0.0 && value != 1.0) return fail(I, RFW_HIP_E_INVALID, "set_option: denoise_motion is 0 (off) or 1");
         if ((uint32_t)value == I->denoise_motion) return RFW_HIP_OK;
         I->denoise_motion = (uint32_t)value;
+        I->dn_images = 0;
+        I->sample_count = 0;
+        I->restart = true;
+    }
+    else if (k == "denoise_deform") { // the temporal option follows skinned meshes (denoise.inc, k_dn_temporal_deform); a changed value drops the history and starts a new image
+        if (value != 0.0 && value != 1.0) return fail(I, RFW_HIP_E_INVALID, "set_option: denoise_deform is 0 (off) or 1");
+        if ((uint32_t)value == I->denoise_deform) return RFW_HIP_OK;
+        I->denoise_deform = (uint32_t)value;
+        I->release_deform(); // (hipFree waits for the frames in flight)
+        for (Instance* c : I->slots) c->release_deform();
         I->dn_images = 0;
         I->sample_count = 0;
         I->restart = true;

@@ -525,6 +525,24 @@ struct Instance {
     DevBuf<uint32_t> d_dn_history_ids[2];
     DevBuf<char> d_dn_snapshot[2], d_dn_motion;
     uint32_t dn_snap_count[2] = {}, dn_motion_count = 0;
+    // option "denoise_deform" (owner; DESIGN.md "Denoiser: deforming meshes"): per slot the triangle plane of the latest sample's primary
+    // hits; in the owner, next to each history, the pose snapshot (four float4 per triangle of every skinned copy, dn_pose_tris of them) and one
+    // uint4 per instance id (dn_snap_count of them) of the frame that wrote it; the device table of the skinned copies with the host copy of
+    // what it holds (it changes only with a synchronize()), and whether the latest temporal frame ran with the option
+    uint32_t denoise_deform = 0;
+    DevBuf<uint2> d_dn_tris;
+    DevBuf<float4> d_dn_pose[2];
+    DevBuf<uint4> d_dn_refs[2], d_dn_copies;
+    std::vector<uint4> dn_copies;
+    uint32_t dn_pose_tris[2] = {};
+    bool dn_deform_latest = false;
+    void release_deform() // (the triangle plane of this instance; in the owner also the snapshots, the per-instance tables and the copies)
+    {
+        d_dn_tris.release(); d_dn_copies.release();
+        for (int q = 0; q < 2; q++) { d_dn_pose[q].release(); d_dn_refs[q].release(); dn_pose_tris[q] = 0; }
+        dn_copies.clear();
+        dn_deform_latest = false;
+    }
     // The display transform (owner; DESIGN.md "Display transform"): the options, the adaptation state — one device record (E, E*, q, N)
     // followed by the 256 counts the latest frame resolved from, allocated at the first frame with automatic exposure — and whether a
     // frame has written it since it was last dropped.  The resolve stages of successive frames are chained through disp_chain, whichever

@@ -239,7 +239,8 @@ int rfw_hip_debug_lbvh_stress(void* inst, uint32_t n, uint32_t iterations, uint3
 // what: "hit0"/"hit1" (uint4), "ray_o0"/"ray_o1", "ray_d0"/"ray_d1", "thr0"/"thr1", "sh_o", "sh_d", "sh_e" (float4), "counters",
 //       "xforms" (InstanceXform), "normals" (InstanceNormal), "ao_rays", "ao_guide" (render modes 5, 6: DESIGN.md "Render modes"),
 //       "dn_guide" (option "denoise": DESIGN.md "Denoiser"), "dn_history" (option "denoise_temporal": DESIGN.md "Denoiser: temporal"),
-//       "dn_ids", "dn_motion" (option "denoise_motion": DESIGN.md "Denoiser: motion"), "ov_prims", "ov_stats" (DESIGN.md "2D layer"),
+//       "dn_ids", "dn_motion" (option "denoise_motion": DESIGN.md "Denoiser: motion"), "dn_tris", "dn_pose" (option "denoise_deform":
+//       DESIGN.md "Denoiser: deforming meshes"), "ov_prims", "ov_stats" (DESIGN.md "2D layer"),
 //       "display_state", "display_hist" (option "tonemap": DESIGN.md "Display transform")
 int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, uint64_t* written)
 {
@@ -269,6 +270,25 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
         HIP_TRY(I, hipStreamSynchronize(I->stream));
         for (Instance* c : I->slots) HIP_TRY(I, hipStreamSynchronize(c->stream));
         if (n) HIP_TRY(I, hipMemcpy(dst, I->d_dn_motion.ptr, n, hipMemcpyDeviceToHost));
+        if (written) *written = n;
+        return RFW_HIP_OK;
+    }
+    if (w == "dn_pose") { // owner state: the pose snapshot the latest temporal frame wrote with option "denoise_deform", behind its header and per-instance table
+        std::vector<char> out;
+        if (I->dn_deform_latest) {
+            const uint32_t h = I->dn_latest;
+            const uint32_t n_inst = (uint32_t)std::min<size_t>(I->dn_snap_count[h], I->d_dn_refs[h].cap);
+            const uint32_t total = (uint32_t)std::min<size_t>(I->dn_pose_tris[h], I->d_dn_pose[h].cap / 4);
+            const uint32_t head[4] = {n_inst, total, 0u, 0u};
+            out.resize(16 + (size_t)n_inst * 16 + (size_t)total * 64);
+            std::memcpy(out.data(), head, 16);
+            HIP_TRY(I, hipStreamSynchronize(I->stream));
+            for (Instance* c : I->slots) HIP_TRY(I, hipStreamSynchronize(c->stream));
+            if (n_inst) HIP_TRY(I, hipMemcpy(out.data() + 16, I->d_dn_refs[h].ptr, (size_t)n_inst * 16, hipMemcpyDeviceToHost));
+            if (total) HIP_TRY(I, hipMemcpy(out.data() + 16 + (size_t)n_inst * 16, I->d_dn_pose[h].ptr, (size_t)total * 64, hipMemcpyDeviceToHost));
+        }
+        const uint64_t n = std::min<uint64_t>(bytes, out.size());
+        if (n) std::memcpy(dst, out.data(), n);
         if (written) *written = n;
         return RFW_HIP_OK;
     }
@@ -366,6 +386,7 @@ int rfw_hip_debug_read(void* inst, const char* what, void* dst, uint64_t bytes, 
     else if (w == "ao_guide") { src = I->d_ao_guide.ptr; avail = (uint64_t)std::min<size_t>((size_t)I->width * I->height, I->d_ao_guide.cap) * 16; } // (faced gN, t) per frame pixel of the latest AO frame; t = 0: the camera ray missed
     else if (w == "dn_guide") { src = I->d_dn_guide.ptr; avail = (uint64_t)std::min<size_t>((size_t)I->width * I->height * 3, I->d_dn_guide.cap) * 16; } // option "denoise": (faced gN, t), (P, 0), (albedo, f) of the latest denoised frame, plane after plane of frame pixels
     else if (w == "dn_ids") { src = I->d_dn_ids.ptr; avail = (uint64_t)std::min<size_t>((size_t)I->width * I->height, I->d_dn_ids.cap) * 4; } // option "denoise_motion": the instance id of the latest sample's primary hit per frame pixel
+    else if (w == "dn_tris") { src = I->d_dn_tris.ptr; avail = (uint64_t)std::min<size_t>((size_t)I->width * I->height, I->d_dn_tris.cap) * 8; } // option "denoise_deform": (triangle row | bit 31 the normal was negated, packed barycentrics) of the latest sample's primary hit per frame pixel
     else if (w == "ov_prims") { src = I->d_ov_tap.ptr; avail = (uint64_t)std::min<size_t>(I->ov_frame_prims, I->d_ov_tap.cap) * sizeof(OvTap); } // the 2D layer: one OvTap per primitive of the latest frame, in draw order
     else if (w == "counters") { src = I->d_counters.ptr + (size_t)I->counter_phase * kMaxSub; avail = sizeof(QueueCounters); }
     else if (w == "tlas_raw") { src = I->d_tlas_raw.ptr; avail = (uint64_t)I->d_tlas_raw.cap * sizeof(Node4); }         // the device-built TLAS before quantisation (entries past the node count are stale)

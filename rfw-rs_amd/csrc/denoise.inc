@@ -15,6 +15,9 @@
 //   k_dn_ids, k_dn_motion, k_dn_temporal_motion  option "denoise_motion" (DESIGN.md "Denoiser: motion"): the instance id of every pixel's primary
 //               hit, one record per instance that carries a point and a normal of this image into the instance's pose of the previous image,
 //               and k_dn_temporal reprojecting through that record, its taps restricted to the same instance.
+//   k_dn_tris, k_dn_pose, k_dn_temporal_deform  option "denoise_deform" (DESIGN.md "Denoiser: deforming meshes"): the triangle and barycentrics of
+//               every pixel's primary hit, a snapshot of the mesh-space vertices of every skinned copy that travels with the history, and
+//               k_dn_temporal reprojecting a skinned copy's pixel through the pose its triangle had in the previous image.
 //
 // Two forms of a pass.  DIRECT: one thread per pixel, 25 taps straight from memory.  TILED: for step s the pixels with equal (x mod s, y mod s)
 // form s^2 sub-images on each of which the pass is a dense 5 x 5 filter; a workgroup takes 16 x 16 pixels of ONE sub-image and stages their
@@ -211,6 +214,54 @@ __global__ __launch_bounds__(256) void k_dn_ids(const CameraParams cam, const Pa
     ids[px] = (int32_t)S.x >= 0 ? S.x : kDnNoId;
 }
 
+// option "denoise_deform".  Per frame pixel the triangle of the primary hit, next to k_dn_ids and with its bounds handling: x = the row of the
+// device triangle buffer (hit[0].y) with bit 31 set iff primary_surface negates the geometric normal, y = the packed barycentrics (hit[0].w)
+constexpr uint32_t kDnFlipped = 0x80000000u;
+__global__ __launch_bounds__(256) void k_dn_tris(const CameraParams cam, const SceneDev sc, const PathDev p, uint2* __restrict__ tris, const uint32_t pixel_mask)
+{
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= p.capacity) return;
+    const uint4 S = p.hit[0][idx];
+    if (S.x == kNoPath) return; // a slab slot without a pixel
+    const uint32_t px = fbits(p.ray_o[0][idx].w) & pixel_mask;
+    if (px >= cam.width * cam.height) return;
+    uint2 out = make_uint2(kDnNoId, 0u);
+    if ((int32_t)S.x >= 0) {
+        const float4 D4 = p.ray_d[0][idx];
+        const float4 q3 = reinterpret_cast<const float4*>(sc.triangles + S.y)[3];
+        const float4* np = reinterpret_cast<const float4*>(sc.instance_normals + (int32_t)S.x);
+        const f3 gN = normalize(xform_rows(np[0], np[1], np[2], mk3(q3.x, q3.y, q3.z), 0.0f)); // primary_surface's, step for step
+        out = make_uint2(S.y | (dot(mk3(D4.x, D4.y, D4.z), gN) >= 0.0f ? kDnFlipped : 0u), S.w);
+    }
+    tris[px] = out;
+}
+
+// One skinned copy of a frame: (first row of the triangle buffer, triangles, first triangle of the pose snapshot, mesh record index); in the
+// table the host builds the copies stand in snapshot order.  Per instance id of a frame (DnCopyRef, next to the snapshot): the first three
+// words of its copy, (0, 0, 0, 0) where the instance is no skinned copy.
+typedef uint4 DnCopy;
+typedef uint4 DnCopyRef;
+
+// The pose snapshot of a history: tp[0..3] of every triangle of every skinned copy (the mesh-space vertices with their w words, the stored
+// geometric normal).  One thread per float4, all copies in one launch.
+__global__ __launch_bounds__(256) void k_dn_pose(const rfw_rt_triangle* __restrict__ triangles, const DnCopy* __restrict__ copies, const uint32_t n_copies,
+                                                 const uint32_t total, float4* __restrict__ out)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (n_copies == 0u || (t >> 2) >= total) return;
+    const uint32_t tri = t >> 2;
+    uint32_t lo = 0u, hi = n_copies; // the last copy that starts at or before tri
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (copies[mid].z <= tri) lo = mid;
+        else hi = mid;
+    }
+    const DnCopy c = copies[lo];
+    const uint32_t local = tri - c.z;
+    if (local >= c.y) return;
+    out[t] = reinterpret_cast<const float4*>(triangles + c.x + local)[t & 3u];
+}
+
 // What a history keeps of every instance of the frame that wrote it, and what k_dn_motion makes of two of them
 struct alignas(16) DnInstance {
     float m[16];       // the forward matrix M, column major (rfw_mat4)
@@ -227,9 +278,13 @@ static_assert(sizeof(DnMotion) == kDnMotionBytes, "DnMotion");
 // One thread per instance of this frame: its record, and its entry of the snapshot that travels with the history this image writes.
 // state 0 = no history (a new, removed or re-meshed instance, a matrix that is not affine, a record that is not finite), 1 = the matrix is the
 // previous image's bit for bit, 2 = moved.  Plain float32, every sum left to right.
+// Option "denoise_deform" (cur_refs != null): the instance's DnCopyRef, and state 3 = deforming — a skinned copy in both images, of the same
+// mesh record and triangle count: the record then holds the rows of the previous forward matrix M' in a and of the previous InstanceNormal
+// in b, for k_dn_temporal_deform to carry the previous pose of the pixel's triangle into the previous image's world.
 __global__ __launch_bounds__(64) void k_dn_motion(const rfw_mat4* __restrict__ matrices, const InstanceXform* __restrict__ xf, const InstanceNormal* __restrict__ nm,
                                                   const uint32_t n, const DnInstance* __restrict__ prev, const uint32_t n_prev, DnInstance* __restrict__ cur,
-                                                  DnMotion* __restrict__ out)
+                                                  DnMotion* __restrict__ out, const DnCopy* __restrict__ copies, const uint32_t n_copies,
+                                                  const DnCopyRef* __restrict__ prev_refs, DnCopyRef* __restrict__ cur_refs)
 {
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     if (i >= n) return;
@@ -242,6 +297,15 @@ __global__ __launch_bounds__(64) void k_dn_motion(const rfw_mat4* __restrict__ m
     c.valid = x.flags & 1u;
     c.pad[0] = c.pad[1] = 0u;
     cur[i] = c;
+    DnCopyRef ref = make_uint4(0u, 0u, 0u, 0u);
+    if (cur_refs != nullptr) {
+        if (c.valid != 0u)
+            for (uint32_t k = 0; k < n_copies; k++) {
+                const DnCopy cp = copies[k];
+                if (cp.w == c.mesh) ref = make_uint4(cp.x, cp.y, cp.z, 0u);
+            }
+        cur_refs[i] = ref;
+    }
     DnMotion r;
     for (int j = 0; j < 3; j++)
         for (int k = 0; k < 4; k++) r.a[j][k] = r.b[j][k] = 0.0f;
@@ -249,7 +313,22 @@ __global__ __launch_bounds__(64) void k_dn_motion(const rfw_mat4* __restrict__ m
     if (prev != nullptr && i < n_prev) {
         const DnInstance q = prev[i];
         const auto affine = [](const float* m) { return fbits(m[3]) == 0u && fbits(m[7]) == 0u && fbits(m[11]) == 0u && fbits(m[15]) == 0x3f800000u; };
-        if (q.valid != 0u && c.valid != 0u && q.mesh == c.mesh && affine(q.m) && affine(c.m)) {
+        const bool linked = q.valid != 0u && c.valid != 0u && q.mesh == c.mesh && affine(q.m) && affine(c.m);
+        const bool deforming = cur_refs != nullptr && prev_refs != nullptr && ref.y != 0u && prev_refs[i].y == ref.y;
+        if (linked && deforming) { // the previous matrix and normal rows as they are: the temporal kernel applies them to the previous pose
+            bool finite = true;
+            for (int j = 0; j < 3; j++) {
+                for (int k = 0; k < 4; k++) {
+                    r.a[j][k] = q.m[4 * k + j];
+                    finite = finite && gl_abs(r.a[j][k]) <= 3.0e38f;
+                }
+                for (int k = 0; k < 3; k++) {
+                    r.b[j][k] = q.n[j][k];
+                    finite = finite && gl_abs(r.b[j][k]) <= 3.0e38f;
+                }
+            }
+            state = finite ? 3u : 0u;
+        } else if (linked) {
             bool same = true;
             for (int k = 0; k < 16; k++) same = same && fbits(q.m[k]) == fbits(c.m[k]);
             const float* inv[3] = {x.inv_r0, x.inv_r1, x.inv_r2}; // row k of inverse(M); its fourth row is (0, 0, 0, 1)
@@ -274,6 +353,13 @@ __global__ __launch_bounds__(64) void k_dn_motion(const rfw_mat4* __restrict__ m
     out[i] = r;
 }
 
+struct DnDeformParams {
+    const uint2* tris;          // this frame's triangle plane (k_dn_tris)
+    const DnCopyRef* refs;      // one per instance id of this frame
+    const DnCopyRef* prev_refs; // ... and of the frame that wrote tp.prev; read only for ids whose state is 3
+    const float4* prev_pose;    // that frame's pose snapshot, four float4 per triangle
+};
+
 struct DnMotionParams {
     const uint32_t* ids;      // this frame's instance ids
     const uint32_t* prev_ids; // those of the frame that wrote tp.prev (null with it)
@@ -283,8 +369,10 @@ struct DnMotionParams {
 };
 
 // k_dn_temporal and, with MOTION, k_dn_temporal_motion: there the hit (P, gN) is first carried into the previous image's pose of its instance
-// (state 2), a tap must show the same instance, and an instance without a record there (state 0) has no history.
-template <bool MOTION> RFW_DI void dn_temporal_pixel(const CameraParams& cam, const DnTemporalParams& tp, const DnMotionParams& mp)
+// (state 2), a tap must show the same instance, and an instance without a record there (state 0) has no history.  With DEFORM,
+// k_dn_temporal_deform: a pixel of a deforming instance (state 3) takes P and gN from its triangle's vertices in the previous image's pose
+// snapshot, at the hit's barycentrics, under the previous instance matrix; from there on it is a state 2 pixel.
+template <bool MOTION, bool DEFORM> RFW_DI void dn_temporal_pixel(const CameraParams& cam, const DnTemporalParams& tp, const DnMotionParams& mp, const DnDeformParams& df)
 {
     const int px = (int)(blockIdx.x * kDnTile + threadIdx.x % kDnTile), py = (int)(blockIdx.y * kDnTile + threadIdx.x / kDnTile);
     if (px >= (int)cam.width || py >= (int)cam.height) return;
@@ -322,6 +410,24 @@ template <bool MOTION> RFW_DI void dn_temporal_pixel(const CameraParams& cam, co
                 const float4 a0 = rp[0], a1 = rp[1], a2 = rp[2], b1 = rp[4], b2 = rp[5];
                 N = normalize(xform_rows(b0, b1, b2, N, 0.0f));
                 P = xform_rows(a0, a1, a2, P, 1.0f);
+            }
+            if (DEFORM && state == 3u) { // the pixel's triangle in the pose and under the matrix of the previous image
+                const uint2 tr = df.tris[i];
+                const DnCopyRef cr = df.refs[id], pr = df.prev_refs[id];
+                const uint32_t local = (tr.x & ~kDnFlipped) - cr.x;
+                state = 0u;
+                if (local < pr.y) { // (a row outside the copy: no history)
+                    const float4* sp = df.prev_pose + 4u * ((size_t)pr.z + local);
+                    const float4 v0 = sp[0], v1 = sp[1], v2 = sp[2], gn = sp[3];
+                    const float u = (float)(tr.y & 65535u) / 65535.0f, v = (float)(tr.y >> 16) / 65535.0f;
+                    const float w = 1.0f - u - v;
+                    const f3 pp = mk3((w * v0.x + u * v1.x) + v * v2.x, (w * v0.y + u * v1.y) + v * v2.y, (w * v0.z + u * v1.z) + v * v2.z);
+                    const float4 a0 = rp[0], a1 = rp[1], a2 = rp[2], b1 = rp[4], b2 = rp[5];
+                    P = xform_rows(a0, a1, a2, pp, 1.0f);
+                    N = normalize(xform_rows(b0, b1, b2, mk3(gn.x, gn.y, gn.z), 0.0f));
+                    if (tr.x & kDnFlipped) N = N * -1.0f;
+                    state = 3u;
+                }
             }
         }
         history = state != 0u;
@@ -380,12 +486,17 @@ template <bool MOTION> RFW_DI void dn_temporal_pixel(const CameraParams& cam, co
 
 __global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal(const CameraParams cam, const DnTemporalParams tp)
 {
-    dn_temporal_pixel<false>(cam, tp, DnMotionParams{});
+    dn_temporal_pixel<false, false>(cam, tp, DnMotionParams{}, DnDeformParams{});
 }
 
 __global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal_motion(const CameraParams cam, const DnTemporalParams tp, const DnMotionParams mp)
 {
-    dn_temporal_pixel<true>(cam, tp, mp);
+    dn_temporal_pixel<true, false>(cam, tp, mp, DnDeformParams{});
+}
+
+__global__ __launch_bounds__(kDnTile * kDnTile) void k_dn_temporal_deform(const CameraParams cam, const DnTemporalParams tp, const DnMotionParams mp, const DnDeformParams df)
+{
+    dn_temporal_pixel<true, true>(cam, tp, mp, df);
 }
 
 void launch_dn_guide(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, float4* guide, uint32_t pixel_mask)
@@ -398,11 +509,22 @@ void launch_dn_ids(hipStream_t s, const CameraParams& cam, const PathDev& p, uin
     if (p.capacity) hipLaunchKernelGGL(k_dn_ids, dim3((p.capacity + 255u) / 256u), dim3(256), 0, s, cam, p, ids, pixel_mask);
 }
 
-void launch_dn_motion(hipStream_t s, const rfw_mat4* matrices, const InstanceXform* xf, const InstanceNormal* nm, uint32_t n, const void* prev, uint32_t n_prev,
-                      void* cur, void* records)
+void launch_dn_tris(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, uint2* tris, uint32_t pixel_mask)
 {
+    if (p.capacity) hipLaunchKernelGGL(k_dn_tris, dim3((p.capacity + 255u) / 256u), dim3(256), 0, s, cam, sc, p, tris, pixel_mask);
+}
+
+void launch_dn_pose(hipStream_t s, const rfw_rt_triangle* triangles, const uint4* copies, uint32_t n_copies, uint32_t total, float4* pose)
+{
+    if (n_copies && total) hipLaunchKernelGGL(k_dn_pose, dim3((4u * total + 255u) / 256u), dim3(256), 0, s, triangles, copies, n_copies, total, pose);
+}
+
+void launch_dn_motion(hipStream_t s, const rfw_mat4* matrices, const InstanceXform* xf, const InstanceNormal* nm, uint32_t n, const void* prev, uint32_t n_prev,
+                      void* cur, void* records, const DnDeformMotion* deform)
+{
+    const DnDeformMotion d = deform ? *deform : DnDeformMotion{};
     if (n) hipLaunchKernelGGL(k_dn_motion, dim3((n + 63u) / 64u), dim3(64), 0, s, matrices, xf, nm, n, static_cast<const DnInstance*>(prev), n_prev,
-                              static_cast<DnInstance*>(cur), static_cast<DnMotion*>(records));
+                              static_cast<DnInstance*>(cur), static_cast<DnMotion*>(records), d.copies, d.n_copies, d.prev_refs, d.cur_refs);
 }
 
 template <bool TILED> static void launch_atrous_pass(hipStream_t s, const CameraParams& cam, const DnParams& dp, bool first, bool last)
@@ -419,7 +541,7 @@ template <bool TILED> static void launch_atrous_pass(hipStream_t s, const Camera
 }
 
 void launch_dn_temporal(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, const float4* prev, float4* cur,
-                        const float prev_view[12], uint32_t samples, uint32_t max_history, const DnMotionLaunch* motion)
+                        const float prev_view[12], uint32_t samples, uint32_t max_history, const DnMotionLaunch* motion, const DnDeformLaunch* deform)
 {
     DnTemporalParams tp;
     tp.acc = acc;
@@ -441,7 +563,16 @@ void launch_dn_temporal(hipStream_t s, const CameraParams& cam, const float4* ac
     mp.cur_ids = motion->cur_ids;
     mp.records = static_cast<const DnMotion*>(motion->records);
     mp.n_records = motion->n_records;
-    hipLaunchKernelGGL(k_dn_temporal_motion, grid, block, 0, s, cam, tp, mp);
+    if (deform == nullptr) {
+        hipLaunchKernelGGL(k_dn_temporal_motion, grid, block, 0, s, cam, tp, mp);
+        return;
+    }
+    DnDeformParams df;
+    df.tris = deform->tris;
+    df.refs = deform->refs;
+    df.prev_refs = deform->prev_refs;
+    df.prev_pose = deform->prev_pose;
+    hipLaunchKernelGGL(k_dn_temporal_deform, grid, block, 0, s, cam, tp, mp, df);
 }
 
 void launch_atrous(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, float4* const planes[2], float4* frame,

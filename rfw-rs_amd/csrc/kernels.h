@@ -137,7 +137,8 @@ void launch_atrous(hipStream_t s, const CameraParams& cam, const float4* acc, ui
 // prev = the previous image's (null: none) and prev_view = pos, p1, right, up of the frame that wrote it; max_history = Hmax, in samples.
 constexpr uint32_t kDenoiseMaxHistory = 64;
 void launch_dn_temporal(hipStream_t s, const CameraParams& cam, const float4* acc, uint64_t slab_elems, const float4* guide, const float4* prev, float4* cur,
-                        const float prev_view[12], uint32_t samples, uint32_t max_history, const struct DnMotionLaunch* motion = nullptr);
+                        const float prev_view[12], uint32_t samples, uint32_t max_history, const struct DnMotionLaunch* motion = nullptr,
+                        const struct DnDeformLaunch* deform = nullptr);
 // option "denoise_motion" (denoise.inc, DESIGN.md "Denoiser: motion").  Ids: where launch_dn_guide is, one uint32 per frame pixel, the instance
 // id of the primary hit (0xffffffff: a miss).  Motion: one thread per instance of the frame's TLAS — its entry of the snapshot `cur`
 // (kDnInstanceBytes each) that travels with the history this image writes, and its record (kDnMotionBytes: rows of A, rows of B, the state's
@@ -152,8 +153,28 @@ struct DnMotionLaunch {
     uint32_t n_records;
 };
 void launch_dn_ids(hipStream_t s, const CameraParams& cam, const PathDev& p, uint32_t* ids, uint32_t pixel_mask);
+// option "denoise_deform" (denoise.inc, DESIGN.md "Denoiser: deforming meshes").  Tris: where launch_dn_ids is, one uint2 per frame pixel: the
+// triangle-buffer row of the primary hit (bit 31: primary_surface negated the geometric normal) and the packed barycentrics; (0xffffffff, 0): a
+// miss.  Pose: tp[0..3] of every triangle of every skinned copy into `pose` (four float4 per triangle), the copies given as a device table of
+// uint4 (first row, triangles, first triangle in `pose`, mesh record index) in `pose` order.  launch_dn_motion with `deform` also writes one
+// uint4 per instance id (first row, triangles, first triangle in the pose snapshot, 0; all 0: no skinned copy) into cur_refs and gives state 3
+// to a skinned copy of both images; launch_dn_temporal with `deform` (and `motion`) runs k_dn_temporal_deform.
+struct DnDeformMotion {
+    const uint4* copies;
+    uint32_t n_copies;
+    const uint4* prev_refs; // null: no history
+    uint4* cur_refs;
+};
+struct DnDeformLaunch {
+    const uint2* tris;
+    const uint4* refs;
+    const uint4* prev_refs;
+    const float4* prev_pose;
+};
+void launch_dn_tris(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, uint2* tris, uint32_t pixel_mask);
+void launch_dn_pose(hipStream_t s, const rfw_rt_triangle* triangles, const uint4* copies, uint32_t n_copies, uint32_t total, float4* pose);
 void launch_dn_motion(hipStream_t s, const rfw_mat4* matrices, const InstanceXform* xf, const InstanceNormal* nm, uint32_t n, const void* prev, uint32_t n_prev,
-                      void* cur, void* records);
+                      void* cur, void* records, const DnDeformMotion* deform = nullptr);
 // The 2D layer (overlay.inc, DESIGN.md "2D layer"): the trait's 2D meshes drawn over the finalised frame, in place, behind whichever of
 // launch_assemble / launch_ao_filter / launch_atrous wrote it.  A draw is one (mesh, instance) pair; draws are sorted by (mesh id, instance
 // index) and the primitives of the frame are their triangles in that order (the draw position).  Three launches per frame:

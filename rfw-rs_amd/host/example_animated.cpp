@@ -11,7 +11,8 @@
 //   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--scale S] [--tonemap K [--auto-exposure]] [--hud] [--out last.ppm]
 //
 // --denoise K (off by default) finalises every frame with K a-trous passes and a history of 16 samples that follows the bouncing
-// instances (options "denoise", "denoise_temporal", "denoise_motion"): every frame here is a new image of one sample per pixel.
+// instances and the skinned actor (options "denoise", "denoise_temporal", "denoise_motion", "denoise_deform"): every frame here is a new
+// image of one sample per pixel.
 // --tonemap K (off by default) passes every frame through the display transform (option "tonemap": 1 exposure only, 2 extended Reinhard,
 // 3 ACES fit), --auto-exposure adapts the exposure to the frames' luminance from frame to frame (option "auto_exposure"); the exposure the
 // last frame was shown with is printed.
@@ -102,7 +103,7 @@ int main(int argc, char** argv)
         std::printf("window %ux%u, scale %g: traced at %ux%u\n", width, height, scale, renderer->render_width(), renderer->render_height());
 
         if (denoise)
-            for (const auto& kv : {std::pair<const char*, double>{"denoise", (double)denoise}, {"denoise_temporal", 16.0}, {"denoise_motion", 1.0}})
+            for (const auto& kv : {std::pair<const char*, double>{"denoise", (double)denoise}, {"denoise_temporal", 16.0}, {"denoise_motion", 1.0}, {"denoise_deform", 1.0}})
                 if (rfw_hip_set_option(renderer->raw(), kv.first, kv.second) != RFW_HIP_OK) throw std::runtime_error(rfw_hip_last_error(renderer->raw()));
 
         if (tonemap)

@@ -11,7 +11,12 @@ rfw_hip_bandwidth_probe reads per second, the yardstick of a pass's 64 algorithm
 non-zero setting k a second time with option "denoise_temporal" = H (DESIGN.md "Denoiser: temporal"), in the same turns; every frame of a
 timed repeat then starts a new image (reset_accumulation), for both, since that is where the history acts.  --denoise-motion 0,1 times
 every temporal setting once per listed value of option "denoise_motion" (DESIGN.md "Denoiser: motion"; 0 never names the option, so that
-a library without it can be timed through RFW_HIP_LIB), in the same turns.
+a library without it can be timed through RFW_HIP_LIB), in the same turns.  --denoise-deform 0,1 does the same for option "denoise_deform"
+(DESIGN.md "Denoiser: deforming meshes"; it needs --denoise-motion with a 1, and acts on the settings whose motion is 1); --scene skinned
+takes the skinned tubes in their room in place of the atrium, and then every frame of a timed repeat takes a new pose (a synchronize() per
+frame, in every setting alike), since that is where the option acts.  With --bandwidth the option's byte floor is printed next to the probe:
+40 B per slab slot for the triangle plane, 128 B per triangle of a skinned copy for k_dn_pose, and 8 B plus up to 64 B of snapshot per
+pixel of a deforming instance for k_dn_temporal_deform (triangles and pixels as the taps of the latest frame count them).
 
 --overlay a,b,c times mode 0 with the 2D layer (DESIGN.md "2D layer"), the settings taking turns: a = a view_2d and no 2D data (the only
 setting a library from before the layer can run: RFW_HIP_LIB), b = a HUD of 2000 textured glyph quads of 12 x 16 pixels (4000 triangles),
@@ -36,6 +41,8 @@ def main():
     ap.add_argument("--denoise-form", type=int, default=0)
     ap.add_argument("--denoise-temporal", type=int, default=0)
     ap.add_argument("--denoise-motion", default="")
+    ap.add_argument("--denoise-deform", default="")
+    ap.add_argument("--scene", default="atrium", choices=("atrium", "skinned"))
     ap.add_argument("--overlay", default="")
     ap.add_argument("--max-path-length", type=int, default=None)  # 1 for the modes (DESIGN.md "Render modes"), 3 with --denoise or --overlay
     ap.add_argument("--bandwidth", action="store_true")
@@ -52,45 +59,65 @@ def main():
     import torch  # (the order bench.py has: torch's HIP runtime first)
     torch.cuda.init()
     from rfw_rs_amd import HipBackend, RenderMode, Scene
-    scene = Scene().build("atrium", a.triangles, 0, 0.0, 0xC0FFEE)
+    scene = Scene().build("atrium", a.triangles, 0, 0.0, 0xC0FFEE) if a.scene == "atrium" else Scene().build("skinned")
     scene.set_aspect(a.width / a.height)
     view = scene.view(a.width, a.height)
     be = HipBackend.init(a.width, a.height, 1.0, max_path_length=a.max_path_length)
     scene.sync(be)
-    what = f"{a.repeats} x {a.frames} frames, {a.width}x{a.height}, atrium of {a.triangles} triangles, max path length {a.max_path_length}"
+    what = f"{a.repeats} x {a.frames} frames, {a.width}x{a.height}, " + (f"atrium of {a.triangles} triangles" if a.scene == "atrium" else "the skinned scene, a pose per frame") + f", max path length {a.max_path_length}"
     if a.denoise:
         passes = [int(k) for k in a.denoise.split(",")]
         motions = [int(m) for m in a.denoise_motion.split(",")] if a.denoise_motion else [0]
         if any(motions) and not a.denoise_temporal:
             ap.error("--denoise-motion needs --denoise-temporal")
-        settings = [(k, 0, 0) for k in passes] + [(k, a.denoise_temporal, m) for k in passes if k and a.denoise_temporal for m in motions]
+        deforms = [int(d) for d in a.denoise_deform.split(",")] if a.denoise_deform else [0]
+        if any(deforms) and not any(motions):
+            ap.error("--denoise-deform needs --denoise-motion with a 1")
+        settings = [(k, 0, 0, 0) for k in passes] + [(k, a.denoise_temporal, m, d) for k in passes if k and a.denoise_temporal for m in motions for d in (deforms if m else [0])]
+        posed = 0
         if any(passes):
             be.set_option("denoise_form", a.denoise_form)
         runs = {s: [] for s in settings}
         for rep in range(-1, a.repeats):  # (-1: the warm-up round of every setting)
-            for k, hmax, motion in settings:
+            for k, hmax, motion, deform in settings:
                 if any(passes):  # (all zero: never name the option, so that a library without it can be timed too)
                     be.set_option("denoise", k)
                 if a.denoise_temporal:
                     be.set_option("denoise_temporal", hmax)
                 if any(motions):
                     be.set_option("denoise_motion", motion)
+                if any(deforms):
+                    be.set_option("denoise_deform", deform)
                 t0 = time.perf_counter()
                 for _ in range(a.warmup if rep < 0 else a.frames):
+                    if a.scene == "skinned":
+                        posed += 1
+                        scene.pose(0.02 * posed)
+                        scene.sync(be)
                     if a.denoise_temporal:
                         be.reset_accumulation()
                     be.render(view)
                 be.framebuffer()
                 if rep >= 0:
-                    runs[(k, hmax, motion)].append((time.perf_counter() - t0) * 1e3 / a.frames)
-        for k, hmax, motion in settings:
-            r = runs[(k, hmax, motion)]
-            print(f"denoise {k} form {a.denoise_form}{f' temporal {hmax}' if hmax else ''}{f' motion {motion}' if hmax and any(motions) else ''}: {statistics.median(r):.3f} ms/frame (min {min(r):.3f}, max {max(r):.3f}; {what})", flush=True)
+                    runs[(k, hmax, motion, deform)].append((time.perf_counter() - t0) * 1e3 / a.frames)
+                    if deform:
+                        ids, state = be.denoise_ids(), be.denoise_motion()[2]
+                        floor = (int(be.denoise_pose()[1].shape[0]), int((state[ids[ids < len(state)]] == 3).sum()))
+        for k, hmax, motion, deform in settings:
+            r = runs[(k, hmax, motion, deform)]
+            print(f"denoise {k} form {a.denoise_form}{f' temporal {hmax}' if hmax else ''}{f' motion {motion}' if hmax and any(motions) else ''}{f' deform {deform}' if hmax and any(deforms) else ''}: "
+                  f"{statistics.median(r):.3f} ms/frame (min {min(r):.3f}, max {max(r):.3f}; {what})", flush=True)
         if a.bandwidth:
             px = a.width * a.height
             print(f"bandwidth probe: {be.bandwidth_probe():.0f} GB/s (read + written); a pass moves 64 B x {px} pixels = {64e-6 * px:.1f} MB"
                   + (f", k_dn_temporal at least 128 B x {px} = {128e-6 * px:.1f} MB" if a.denoise_temporal else "")
                   + (f", k_dn_temporal_motion up to 24 B x {px} = {24e-6 * px:.1f} MB more, k_dn_ids 36 B per slab slot" if any(motions) else ""), flush=True)
+            if any(deforms) and any(passes):
+                gbs = be.bandwidth_probe()
+                tris, pixels = floor
+                nbytes = 40 * px + 128 * tris + 72 * pixels
+                print(f"denoise_deform floor: k_dn_tris 40 B x {px} slab slots, k_dn_pose 128 B x {tris} triangles, k_dn_temporal_deform up to 72 B x {pixels} pixels of deforming instances "
+                      f"= {nbytes / 1e6:.2f} MB = {nbytes / gbs / 1e3:.2f} us at the probe's {gbs:.0f} GB/s", flush=True)
         be.close()
         return
     if a.overlay:
