@@ -223,7 +223,8 @@ RFW_HIP_API int rfw_hip_set_3d_instances(void* instance, uint32_t mesh, const rf
 /* :49 set_materials — `changed` (here and in every call below that takes one): bit k of word k / 32 = element k, NULL = everything; the
  * array must cover all `num` elements ((num + 31) / 32 words) — a clear bit means the element is not looked at. */
 RFW_HIP_API int rfw_hip_set_materials(void* instance, const rfw_device_material* materials, uint32_t num, const uint32_t* changed);
-/* :53 set_textures — sampled by shade for diffuse and normal maps (the two maps shade.comp reads).  `changed` (bit k = texture k, may be NULL =
+/* :53 set_textures — sampled by shade for diffuse and normal maps (the two maps shade.comp reads; with option "material_maps" the
+ * metallic-roughness, sheen and emissive maps too).  `changed` (bit k = texture k, may be NULL =
  * all): with the same number of textures as before, textures whose bit is clear are not read at all, and synchronize() uploads only the
  * changed ones. */
 RFW_HIP_API int rfw_hip_set_textures(void* instance, const rfw_texture_data* textures, uint32_t num, const uint32_t* changed);
@@ -298,7 +299,26 @@ RFW_HIP_API int rfw_hip_synchronize(void* instance);
  * the formula is "denoise_motion"'s.  An instance that gains or loses its skin, or whose skinned copy changes its mesh or triangle count,
  * starts without history.  Without a skinned copy in the scene the frame equals the one with the option off bit for bit.  A different value
  * drops the history and starts a new image; any other value is RFW_HIP_E_INVALID.  Out of scope: morph targets, vertices moved by
- * rfw_hip_set_3d_mesh re-sends, camera-ray jitter.  Off, nothing is allocated, launched or written for it. */
+ * rfw_hip_set_3d_mesh re-sends, camera-ray jitter.  Off, nothing is allocated, launched or written for it.
+ * Option "material_maps" = 0 (off, the default) | 1: wherever the shade kernel runs — rfw_hip_render mode 0 and unknown modes,
+ * rfw_hip_render_samples, rfw_hip_render_batch; every frame slot, with sub-streams, on sharded instances (shading is local to a rank) — the
+ * materials' metallic_roughness_map, sheen_map and emissive_map are read, which shade.comp tests the flags of and never reads (DESIGN.md
+ * "Material maps").  A map is live when its flag bit is set and 0 <= index < the number of textures, as the diffuse map; lambda, tu, tv are
+ * the diffuse map's.  In single uncontracted float32 operations, behind the diffuse and normal map reads:
+ *   metallic-roughness (RFW_MAT_HAS_ROUGHNESS_MAP | RFW_MAT_HAS_METALLIC_MAP): c = the normal map's sampler at (tu, tv), level (float)(int)lambda
+ *     (bilinear at level 0, nearest above; R, G, B after the format's swizzle); with the roughness bit roughness = max(0.01, r * c.g), r the
+ *     scalar byte / 255 before its floor; with the metallic bit metallic = metallic * c.b (glTF's channels and meaning: factor times texel)
+ *   sheen (RFW_MAT_HAS_SHEEN_MAP): the same sampler, sheen = sheen * c.r
+ *   emissive (RFW_MAT_HAS_EMISSIVE_MAP): live only on a material no colour component of which exceeds 1 (its triangles are in no light list).
+ *     c = the diffuse map's trilinear fetch; where the ray arrives on the front side (dot(D, gN) < 0, gN the geometric normal before the
+ *     back-facing flip) throughput * c.rgb * (1 / bsdfPdf), clamped by "clamp_value", is added to the pixel — at every bounce, weight 1:
+ *     next-event estimation never samples these triangles — and the hit is then shaded as a surface as before.  A material with an
+ *     emissive map AND a colour component above 1 keeps its behaviour in full (a uniform area light to next-event estimation, a surface at hits).
+ * Off, every frame is what it was bit for bit and the kernels launched are the ones of before; on, a scene whose synchronized materials
+ * carry none of the four flag bits still launches those.  A different value restarts accumulation; any other value is RFW_HIP_E_INVALID.
+ * Modes 1-6 and the denoiser's guide (albedo, pass-through flag) do not change.  Out of scope: the alpha cut-out of the diffuse map (it needs
+ * any-hit work in the traversal); textured radiance for area lights (an emissive map on a material whose colour exceeds 1, with next-event
+ * estimation towards it); pass-through of emissive-mapped pixels in the denoiser (their emission is filtered with the rest); maps in modes 1-6. */
 enum {
     RFW_HIP_RENDER_DEFAULT = 0,
     RFW_HIP_RENDER_NORMAL = 1,
@@ -339,6 +359,7 @@ RFW_HIP_API int rfw_hip_reset_accumulation(void* instance);
  *                  "denoise" 0 (off, default) | 1 ... 5 a-trous passes over the path-traced frame, "denoise_colour" (> 0),
  *                  "denoise_temporal" 0 (off, default) | 1 ... 64 samples of history across images, "denoise_motion" 0 (off, default) | 1
  *                  the history follows moving instances, "denoise_deform" 0 (off, default) | 1 the history follows skinned meshes,
+ *                  "material_maps" 0 (off, default) | 1 the metallic-roughness, sheen and emissive maps of the materials are honoured,
  *                  "sample_offset" 0 (default) ... 2^24, the first sample index of every
  *                  image — any other value of these is RFW_HIP_E_INVALID; see rfw_hip_render; "scale_filter" 0 nearest | 1 (default)
                   bilinear / area: how the render-size frame becomes the window-size one (see rfw_hip_create); the display transform:
@@ -507,7 +528,9 @@ RFW_HIP_API int rfw_hip_debug_lbvh_stress(void* instance, uint32_t num_boxes, ui
  * and 12 output floats.  op 0: BSDFEval -> rgb (gpu-rt/shaders/disney.glsl:110-195); 1: BSDFPdf -> pdf (:89-108); 2: BSDFSample -> wi.xyz,
  * pdf, type (:197-263); 3: CalculateLightPDF -> pdf (shade.comp:325-328); 4: RandomPointOnLight with the lights set on this instance
  * (synchronize first) -> P.xyz, pickProb, lightPdf, colour.rgb, picked light (shade.comp:413-528); 5: RandomBarycentrics(r0 = [41]) -> barycentrics
- * (shade.comp:371-411). */
+ * (shade.comp:371-411); 6: the map step of option "material_maps" (see rfw_hip_render; applied whatever the option says) under the textures
+ * set on this instance (synchronize first), with tu = [27], tv = [28], lambda = [29] -> metallic, roughness, sheen, Le.rgb (the emissive
+ * map's texel, 0 where it is not live), emissive map live (0 / 1) (tests/test_gpu_material_maps.py compares with a numpy restatement). */
 RFW_HIP_API int rfw_hip_debug_eval_shading(void* instance, int op, uint64_t n, const float* in48, float* out12);
 
 /* Test-only: the display transform (option "tonemap", see rfw_hip_render) on a caller-supplied frame of w x h float4 pixels — the very

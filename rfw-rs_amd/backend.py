@@ -248,8 +248,14 @@ class HipBackend:
         self._check(self._l.rfw_hip_set_3d_instances(self._h, mesh, C.byref(instances)))
 
     def set_materials(self, materials, changed=None):
+        """changed: optional list of indices whose bit is set in the trait's `changed` BitSlice (None: everything)."""
         arr = (pod.DeviceMaterial * len(materials))(*materials)
-        self._check(self._l.rfw_hip_set_materials(self._h, arr, len(materials), None))
+        bits = None
+        if changed is not None:
+            bits = (C.c_uint32 * ((len(materials) + 31) // 32 or 1))()
+            for k in changed:
+                bits[k // 32] |= 1 << (k % 32)
+        self._check(self._l.rfw_hip_set_materials(self._h, arr, len(materials), bits))
 
     def set_textures(self, textures, changed=None):
         """changed: optional list of indices whose bit is set in the trait's `changed` BitSlice (None: everything)."""

@@ -353,6 +353,8 @@ int do_render(Instance* I, const rfw_camera_view_3d* views, uint32_t k, bool sam
             const Instance* O = scene_of(I);
             const int g = O->shade_group;
             if (g == 256 || (g == 0 && k == 1 && !O->slots.empty())) cam[s].flags |= kFlagShadeSmallGroups;
+            // option "material_maps": k_shade_maps in k_shade's place only where the table this frame reads holds a parameter map
+            if (O->material_maps && O->mat_param_maps) cam[s].flags |= kFlagMaterialMaps;
         }
     }
     BatchViews bv;
@@ -1043,6 +1045,13 @@ int rfw_hip_set_option(void* inst, const char* key, double value)
         I->release_deform(); // (hipFree waits for the frames in flight)
         for (Instance* c : I->slots) c->release_deform();
         I->dn_images = 0;
+        I->sample_count = 0;
+        I->restart = true;
+    }
+    else if (k == "material_maps") { // k_shade honours the metallic-roughness, sheen and emissive maps (shade_device.h, apply_parameter_maps); a changed value starts a new image
+        if (value != 0.0 && value != 1.0) return fail(I, RFW_HIP_E_INVALID, "set_option: material_maps is 0 (off) or 1");
+        if ((uint32_t)value == I->material_maps) return RFW_HIP_OK;
+        I->material_maps = (uint32_t)value;
         I->sample_count = 0;
         I->restart = true;
     }

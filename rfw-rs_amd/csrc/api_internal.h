@@ -287,6 +287,12 @@ struct Instance {
     std::map<uint32_t, MeshHost> meshes;
     std::map<uint32_t, InstList> inst_lists;
     std::vector<rfw_device_material> materials;
+    // option "material_maps" (0 off, 1): k_shade reads the metallic-roughness, sheen and emissive maps — through its twin k_shade_maps, which
+    // do_render selects only while the SYNCHRONIZED material table holds a material with one of those flag bits (mat_param_maps; set_materials
+    // counts them in what it was handed, upload_tables makes that the table's)
+    uint32_t material_maps = 0;
+    uint32_t mat_param_maps_pending = 0, mat_param_maps = 0;
+    std::vector<uint8_t> mat_has_param_map; // per material of the table as handed over so far (elements under clear `changed` bits keep theirs)
     std::vector<rfw_area_light> area_lights;
     std::vector<rfw_point_light> point_lights;
     std::vector<rfw_spot_light> spot_lights;

@@ -1132,6 +1132,7 @@ int upload_tables(Instance* I)
     if ((rc = write_table(I, dst.dir, dst.n_dir, old.dir, old.n_dir, I->directional_lights, I->dir_dirty))) return rc;
     HIP_TRY(I, hipEventRecord(I->tables_ready, I->upload_stream));
     I->tables_version = nv;
+    I->mat_param_maps = I->mat_param_maps_pending; // (option "material_maps": what the table the next frames read holds)
     I->mat_dirty.clear(); I->area_dirty.clear(); I->point_dirty.clear(); I->spot_dirty.clear(); I->dir_dirty.clear();
     return RFW_HIP_OK;
 }
@@ -1819,6 +1820,17 @@ int rfw_hip_set_materials(void* inst, const rfw_device_material* m, uint32_t n, 
 {
     LOCK(inst);
     if (n && !m) return fail(I, RFW_HIP_E_INVALID, "set_materials: null data");
+    // option "material_maps": which materials OF THE TABLE AS IT WILL BE UPLOADED carry a metallic-roughness, sheen or emissive map flag — an
+    // element whose `changed` bit is clear is not looked at here either (write_table keeps the device's copy of it), so the count
+    // upload_tables makes the synchronized table's is exact whatever the caller left under clear bits
+    constexpr uint32_t kParamMaps = RFW_MAT_HAS_ROUGHNESS_MAP | RFW_MAT_HAS_METALLIC_MAP | RFW_MAT_HAS_EMISSIVE_MAP | RFW_MAT_HAS_SHEEN_MAP;
+    const bool partial = changed && I->materials.size() == n && I->mat_has_param_map.size() == n; // (mark_dirty's rule)
+    I->mat_has_param_map.resize(n);
+    I->mat_param_maps_pending = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!partial || (changed[i >> 5] & (1u << (i & 31u)))) I->mat_has_param_map[i] = (m[i].flags & kParamMaps) != 0u;
+        I->mat_param_maps_pending += I->mat_has_param_map[i];
+    }
     mark_dirty(I->mat_dirty, I->materials.size(), n, changed);
     I->materials.assign(m, m + n);
     I->materials_dirty = I->materials_dirty || I->mat_dirty.any;

@@ -73,6 +73,8 @@ void launch_primary(hipStream_t s, const CameraParams& cam, const SceneDev& sc, 
 void launch_primary_batch(hipStream_t s, const CameraParams& cam, const BatchViews& views, const SceneDev& sc, const PathDev& p, bool count);
 void launch_extend(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, uint32_t bounce, bool count, const uint32_t* order = nullptr);
 void launch_extension_keys(hipStream_t s, const SceneDev& sc, const PathDev& p, uint32_t bounce, uint32_t* keys, uint32_t* vals);
+// (cam.flags: kFlagShadeSmallGroups picks the workgroup size, kFlagMaterialMaps the twin (k_shade_maps) that reads the materials' metallic-roughness,
+// sheen and emissive maps — option "material_maps"; without the flag the kernels launched are the ones that never heard of it)
 void launch_shade(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, uint32_t bounce);
 void launch_shadow(hipStream_t s, const CameraParams& cam, const SceneDev& sc, const PathDev& p, uint32_t bounce, bool count);
 void launch_copy_f4(hipStream_t s, const float4* src, float4* dst, uint64_t n); // bandwidth probe

@@ -82,11 +82,15 @@ struct ShadingData {
     f3 cspec0; // prepare_tint(): Cspec0 of BSDFEval from the (textured) colour
     uint32_t flags;
     int32_t diffuse_map, normal_map;
+    // option "material_maps" (apply_parameter_maps below): filled by extractParameters<true> only — the other three slots of the material and
+    // the roughness scalar before its floor
+    int32_t metallic_roughness_map, emissive_map, sheen_map;
+    float roughness_scalar;
 };
 RFW_DI float CHAR2FLT(uint32_t x, int s) { return (float)((x >> s) & 255u) * (1.0f / 255.0f); }
-RFW_DI ShadingData extractParameters(const rfw_device_material* m)
+template <bool MAPS = false> RFW_DI ShadingData extractParameters(const rfw_device_material* m)
 {
-    // 96-B material = 6 dwordx4 loads
+    // 96-B material = 6 dwordx4 loads (the sixth, the emissive and sheen slots, only with MAPS)
     const float4* mp = reinterpret_cast<const float4*>(m);
     const float4 c = mp[0], a = mp[1], s = mp[2];
     const uint4 p = *reinterpret_cast<const uint4*>(mp + 3);
@@ -95,6 +99,13 @@ RFW_DI ShadingData extractParameters(const rfw_device_material* m)
     d.flags = q.x;
     d.diffuse_map = (int32_t)q.y;
     d.normal_map = (int32_t)q.z;
+    if constexpr (MAPS) {
+        const uint4 q5 = *reinterpret_cast<const uint4*>(mp + 5);
+        d.metallic_roughness_map = (int32_t)q.w;
+        d.emissive_map = (int32_t)q5.x;
+        d.sheen_map = (int32_t)q5.y;
+        d.roughness_scalar = CHAR2FLT(p.x, 24);
+    }
     d.color = mk3(c.x, c.y, c.z);
     d.absorption = mk3(a.x, a.y, a.z);
     d.specular = mk3(s.x, s.y, s.z);
@@ -410,6 +421,32 @@ RFW_DI f4 fetchTexelTrilinear(const uint32_t* __restrict__ data, const TexDesc& 
     const f4 p0 = texture_sample(data, t, u, v, (float)level0);
     const f4 p1 = texture_sample(data, t, u, v, (float)level1);
     return (1.0f - f) * p0 + f * p1;
+}
+
+// ---- option "material_maps" (DESIGN.md "Material maps"): the three parameter maps shade.comp tests the flags of and never reads, with glTF's
+// meaning (factor x texel, G roughness, B metalness: what backends/wgpu/shaders/deferred.frag takes).  A map is live when its flag bit is set
+// and 0 <= index < n_textures, as the diffuse map; the emissive map only on a material no colour component of which exceeds 1 (`dim`: such
+// a triangle is in no light list).  `sd` comes from extractParameters<true>; lambda, tu, tv are k_shade's.  Returns whether the emissive map is
+// live, with its texel in `Le` (else 0).  Every line one float32 operation.
+RFW_DI bool apply_parameter_maps(ShadingData& sd, const bool dim, const uint32_t* __restrict__ tex_data, const TexDesc* __restrict__ tex_desc,
+                                 const uint32_t n_textures, const float lambda, const float tu, const float tv, f3& Le)
+{
+    if ((sd.flags & (RFW_MAT_HAS_ROUGHNESS_MAP | RFW_MAT_HAS_METALLIC_MAP)) && sd.metallic_roughness_map >= 0 && (uint32_t)sd.metallic_roughness_map < n_textures) {
+        const f4 c = texture_sample(tex_data, tex_desc[sd.metallic_roughness_map], tu, tv, (float)f2i(lambda));
+        if (sd.flags & RFW_MAT_HAS_ROUGHNESS_MAP) sd.roughness = gl_max(0.01f, sd.roughness_scalar * c.y);
+        if (sd.flags & RFW_MAT_HAS_METALLIC_MAP) sd.metallic = sd.metallic * c.z;
+    }
+    if ((sd.flags & RFW_MAT_HAS_SHEEN_MAP) && sd.sheen_map >= 0 && (uint32_t)sd.sheen_map < n_textures) {
+        const f4 c = texture_sample(tex_data, tex_desc[sd.sheen_map], tu, tv, (float)f2i(lambda));
+        sd.sheen = sd.sheen * c.x;
+    }
+    Le = mk3(0.0f);
+    if (dim && (sd.flags & RFW_MAT_HAS_EMISSIVE_MAP) && sd.emissive_map >= 0 && (uint32_t)sd.emissive_map < n_textures) {
+        const f4 c = fetchTexelTrilinear(tex_data, tex_desc[sd.emissive_map], lambda, tu, tv);
+        Le = mk3(c.x, c.y, c.z);
+        return true;
+    }
+    return false;
 }
 
 // ---- shade.comp:283-528 (uniform light pick: ISLIGHTS undefined) ----

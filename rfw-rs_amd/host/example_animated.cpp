@@ -8,7 +8,7 @@
 // Where the reference presents to a window, this program downloads the presented (Bgra8UnormSrgb) frame of every frame into a ring of
 // pinned host buffers without stalling the frames in flight, and writes the last one as a PPM image.
 //
-//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--scale S] [--tonemap K [--auto-exposure]] [--hud] [--out last.ppm]
+//   example_animated [--gltf scene.glb | scene.obj] [--actor animated.gltf]... [--frames N] [--size WxH] [--spheres NXxNZ] [--path-length L] [--denoise K] [--scale S] [--tonemap K [--auto-exposure]] [--material-maps] [--hud] [--out last.ppm]
 //
 // --denoise K (off by default) finalises every frame with K a-trous passes and a history of 16 samples that follows the bouncing
 // instances and the skinned actor (options "denoise", "denoise_temporal", "denoise_motion", "denoise_deform"): every frame here is a new
@@ -16,6 +16,9 @@
 // --tonemap K (off by default) passes every frame through the display transform (option "tonemap": 1 exposure only, 2 extended Reinhard,
 // 3 ACES fit), --auto-exposure adapts the exposure to the frames' luminance from frame to frame (option "auto_exposure"); the exposure the
 // last frame was shown with is printed.
+// --material-maps (off by default) has the path tracer honour the materials' metallic-roughness, sheen and emissive maps (option
+// "material_maps"); how many of the scene's materials have such a map that is live (its texture exists; an emissive map only on a material no
+// colour component of which exceeds 1) is printed.
 // --hud (off by default) draws the frame counter and the frame time over the image the way rfw-font draws the reference's FPS counter: one
 // atlas texture (white, the glyphs in alpha, one mip level), one 2D mesh of glyph quads rewritten every frame, one 2D instance with the
 // pixel-space matrix, and the frame's Camera2D view (line 1: "frame N", line 2: "T ms" of the frame before).
@@ -35,7 +38,7 @@ int main(int argc, char** argv)
     std::string gltf, out = "example_animated.ppm";
     std::vector<std::string> actors;
     uint32_t frames = 240, width = 1280, height = 720, nx = 100, nz = 100, path_length = 2, denoise = 0, tonemap = 0;
-    bool hud = false, auto_exposure = false;
+    bool hud = false, auto_exposure = false, material_maps = false;
     double scale = 1.0; // rfw's Settings::scale_mode = Custom(S): traced at size x S, presented at size
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -50,6 +53,7 @@ int main(int argc, char** argv)
         else if (a == "--scale") scale = std::atof(next());
         else if (a == "--tonemap") tonemap = (uint32_t)std::atoi(next());
         else if (a == "--auto-exposure") auto_exposure = true;
+        else if (a == "--material-maps") material_maps = true;
         else if (a == "--hud") hud = true;
         else if (a == "--out") out = next();
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -109,6 +113,16 @@ int main(int argc, char** argv)
         if (tonemap)
             for (const auto& kv : {std::pair<const char*, double>{"tonemap", (double)tonemap}, {"auto_exposure", auto_exposure ? 1.0 : 0.0}})
                 if (rfw_hip_set_option(renderer->raw(), kv.first, kv.second) != RFW_HIP_OK) throw std::runtime_error(rfw_hip_last_error(renderer->raw()));
+
+        if (material_maps) {
+            if (rfw_hip_set_option(renderer->raw(), "material_maps", 1.0) != RFW_HIP_OK) throw std::runtime_error(rfw_hip_last_error(renderer->raw()));
+            const int32_t n_tex = (int32_t)scene.textures.size();
+            auto exists = [&](int32_t t) { return t >= 0 && t < n_tex; };
+            uint32_t live = 0;
+            for (const rfw::Material& m : scene.materials)
+                if (exists(m.metallic_roughness_tex) || exists(m.sheen_tex) || (exists(m.emissive_tex) && !(m.color[0] > 1.0f || m.color[1] > 1.0f || m.color[2] > 1.0f))) live++;
+            std::printf("material maps: %u of %zu materials have a live metallic-roughness, sheen or emissive map\n", live, scene.materials.size());
+        }
 
         const uint64_t px = (uint64_t)width * height;
         std::vector<uint32_t*> ring(8, nullptr); // presented frames land here, 8 frames of slack
